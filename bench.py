@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's headline metric on MI355X: denoise-UNet sampling steps/s at 256x256 pixel-space BBDM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c5] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4|c5] [--dump-outputs DIR] [--full [--no-cpu]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,11 @@ Multi-GPU: one process per GPU, image pairs shard naturally: ev
 data-path collective ("weak" scaling); the timed region is bracketed by barrier + synchronize on both sides and the
 MAX over ranks is taken; value = steps all ranks completed / that time.
 
-Rank 0 prints ONE JSON line with, besides the contract fields,
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when --dump-outputs DIR is given
+(DIR/<name>.npy, float32: x_tminus and x0_recon of p_sample; c4: the loss and a strided sample of the updated weights) and prints
+ONE JSON line with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+
+With --full, rank 0's line carries besides them (and the default c2 run also times c1, c3, c5 and c4 after the headline)
   roofline     : the dominant kernel -- the Winograd tile GEMMs on gemm_bf3p_pipe_kernel<NP = 2> (fp32-grade products on the 16-bit
                  matrix core: two fp16 planes per operand under a provable scale, THREE f16 MFMA terms per product, csrc/h2_split.h;
                  with UNetModel.gemm_h2 = False the six-term bf16x3 planes) -- fp32-equivalent FLOPs per launch / average launch
@@ -136,9 +140,9 @@ def make_inputs(batch, ch, size, seed=1234):
 
 
 def _reference_model(up, skip, sstep, sd):
-    """The reference's own BrownianBridgeModel (CPU) with our state_dict, when /root/reference is mounted (the build
-    container); None on the GPU box.  Never part of the product path: bench.py's cpu_baseline leg only."""
-    ref_root = os.environ.get("BBDM_REFERENCE_ROOT", "/root/reference")
+    """The reference's own BrownianBridgeModel (CPU) with our state_dict, when BBDM_REFERENCE_ROOT names a checkout of it; else
+    None.  Never part of the product path: bench.py's cpu_baseline leg only."""
+    ref_root = os.environ.get("BBDM_REFERENCE_ROOT", "")
     if not os.path.isdir(os.path.join(ref_root, "model", "BrownianBridge")):
         return None
     try:
@@ -206,7 +210,7 @@ def _parity_record(g_a, g_b, a_ref, b_ref, i_par, kind):
 
 
 def cpu_baseline(workload, sd, budget_s=30.0, parity_inputs=None):
-    """the reference's CPU path (imported from /root/reference when mounted -> kind "reference", else
+    """the reference's CPU path (imported from BBDM_REFERENCE_ROOT when set -> kind "reference", else
     the validated restatement oracle/bbdm_oracle.py -> kind "port") timed on this box's host cores.
 
     Bounded sample of the workload: ONE image of the batch at the workload's resolution (a 256x256 batch-16 CPU step
@@ -430,7 +434,30 @@ def parse_args(argv=None):
                     help="skip the eager per-launch-event pass after the timed region (rocprofv3 traces of the graph replay alone)")
     ap.add_argument("--no-extras", action="store_true",
                     help="headline run (c2, one GPU): do not time the other BASELINE.json configs (c1, c3, c5, c4) after it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: roofline and per-kernel times (eager profiled pass), the A/B "
+                         "plans, parity against the CPU path, cpu_baseline, first-stage pipeline, the other BASELINE.json configs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0):
+    """Write ``arrays`` (name -> tensor) as ``out_dir/<name>.npy`` in float32 (float64 stays float64).  An array larger than its
+    share of DUMP_BUDGET_BYTES is written as a fixed, seeded sample of its flattened elements (sorted indices, seed 0)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}{'' if rank == 0 else f'_rank{rank}'}.npy"), np.ascontiguousarray(a))
 
 
 # the other BASELINE.json configs, timed after the headline in the default run: (workload, warm-up, timed steps)
@@ -470,15 +497,15 @@ def main():
     env = (rank, local_rank, world, dev, dist)
 
     line = run_workload(args, env)
-    # The default run (`python bench.py --gpus 1`) also times the other four BASELINE.json configs after the headline, so that every
-    # configuration's step time, whole-step roofline fraction and parity sample are in the ONE line the driver records (they were
-    # builder-run numbers in rounds 1-3).  Same code path as `--workload cN`; the cpu_baseline timing leg is the headline's only.
-    if args.workload == "c2" and world == 1 and not args.no_extras and line is not None:
+    # The full run (`python bench.py --gpus 1 --full`) also times the other four BASELINE.json configs after the headline, so that every
+    # configuration's step time, whole-step roofline fraction and parity sample are in ONE line.  Same code path as
+    # `--workload cN`; the cpu_baseline timing leg is the headline's only.
+    if args.full and args.workload == "c2" and world == 1 and not args.no_extras and line is not None:
         line["workloads"] = {}
         for w, wu, st in EXTRA_WORKLOADS:
             torch.cuda.empty_cache()
             sub = argparse.Namespace(**vars(args))
-            sub.workload, sub.warmup, sub.steps, sub.no_cpu, sub.dump_ops = w, wu, st, True, None
+            sub.workload, sub.warmup, sub.steps, sub.no_cpu, sub.dump_ops, sub.dump_outputs = w, wu, st, True, None, None
             t0 = time.perf_counter()
             r = run_workload(sub, env)
             line["workloads"][w] = {
@@ -489,7 +516,7 @@ def main():
                 "kernel_ms_per_step": r["kernel_ms_per_step"], "parity": r["parity"], "pipeline": r.get("pipeline"),
                 "training": r.get("training"), "winograd6_ms_per_step": r.get("winograd6_ms_per_step"),
                 "wall_s": time.perf_counter() - t0}
-    if rank == 0 and line is not None:
+    if rank == 0 and line is not None and args.full:
         # LAST key of the line (the driver's stored record keeps the tail of stdout): every configuration's step time, whole-step
         # roofline fraction and worst parity error in <= 400 characters -- [ms_per_step, frac_step, worst rel_err]
         def _brief(r, frac):
@@ -515,10 +542,28 @@ def main():
         if c4r.get("winograd6_ms_per_step"):         # the training micro-step on the m <= 6 tiles (UNetModel.winograd_train8 = 0)
             line["summary"]["c4_m6"] = round(c4r["winograd6_ms_per_step"], 3)
         line["summary"]["units"] = "[ms_per_step, frac_step, worst parity rel_err]"
+    if rank == 0 and line is not None:
         print(json.dumps(line))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def _dtype(plan, training):
+    """The line's `dtype`: what the tile GEMMs of the timed plan run on (the entry points its ops are bound to)."""
+    all_ops = list(plan.ops) + (list(plan.bops) if training else [])
+    entries = [getattr(nm, "entry", "") for nm, _ in all_ops if nm == "bbdm_winograd_gemm_f32"]
+    h2_ops = sum("_h2p_" in e for e in entries)
+    bf3p_ops, bf3_ops = sum(e.endswith("bf3p_f32") or "bf3p_splitk" in e for e in entries), sum(e.endswith("bf3_f32") for e in entries)
+    if h2_ops + bf3p_ops + bf3_ops == 0:
+        return "f32"
+    if h2_ops > bf3p_ops + bf3_ops:
+        return ("f32 (tile GEMMs: fp32 operands as two fp16 planes under a provable power-of-two scale, 3 fp16-MFMA terms, fp32 "
+                "accumulate -- measured against fp64 MORE accurate than the six-term bf16x3 split and than the f32 MFMA; 1x1 layers "
+                "(skip / qkv / proj_out) and the long-sequence attention: the same pair; short-sequence, cross- and training "
+                "attention: bf16x3; all other kernels native fp32)")
+    return ("f32 (tile GEMMs: fp32 operands split exactly into 3 bf16, 6 bf16-MFMA terms, fp32 accumulate -- fp32-accurate; "
+            "all other kernels native fp32)")
 
 
 def run_workload(args, env):
@@ -587,7 +632,8 @@ def run_workload(args, env):
             return loss.detach().reshape(1)
     else:
         def step(i, img):
-            out, _ = model.p_sample(img, y, ctx, i % (nsteps_table - 1), clip_denoised=False)
+            out, x0_recon = model.p_sample(img, y, ctx, i % (nsteps_table - 1), clip_denoised=False)
+            state["x0_recon"] = x0_recon
             return out
 
     state = {"img": x_t}
@@ -603,7 +649,7 @@ def run_workload(args, env):
     # latents in rounds 1-2, every inference plan since round 3) -- there the timed region is the plain product path and the events come from a second,
     # eager pass of the same K steps.
     plan_graph = (not training) and next(iter(model.denoise_fn._plans.values()))._want_graph()
-    model.denoise_fn.op_profile = None if (training or plan_graph) else prof
+    model.denoise_fn.op_profile = None if (training or plan_graph or not args.full) else prof
 
     marks = []          # training: a HIP event after every timed micro-step (boundary vs non-boundary step time, see `training` below)
 
@@ -623,6 +669,16 @@ def run_workload(args, env):
     if training:
         opt_events.clear()
     elapsed = dist_utils.timed_region((lambda: timed(marks)) if training else timed, dist, dev)
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step -- sampling: p_sample's (x_{t-1}, x0_recon); training: the
+        # micro-step's loss, plus a fixed strided sample (<= 4096 values per tensor) of the UNet parameters the optimizer steps updated
+        if training:
+            outs = {"loss": state["img"],
+                    "params_sample": torch.cat([p.detach().reshape(-1)[::max(1, p.numel() // 4096)][:4096]
+                                                for p in model.denoise_fn.parameters()])}
+        else:
+            outs = {"x_tminus": state["img"], "x0_recon": state["x0_recon"]}
+        dump_outputs(args.dump_outputs, outs, rank)
     training_info = None
     if training:
         # Per-micro-step times from the events: the accumulation BOUNDARY micro-step carries the gradient all-reduce (DDP; the other
@@ -640,14 +696,14 @@ def run_workload(args, env):
                          "optimizer_step_ms": mean(opt_ms),
                          "allreduce_exposed_ms": (mean(bnd) - mean(non) - (mean(opt_ms) or 0.0)) if (bnd and non and world > 1) else None,
                          "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if world > 1 else None}
-        if world > 1 and not sync_every[0]:
+        if args.full and world > 1 and not sync_every[0]:
             sync_every[0] = True
             for i in range(args.accumulate):
                 state["img"] = step(prime + args.warmup + args.steps + i, state["img"])
             training_info["sync_every_micro_step_ms_per_step"] = dist_utils.timed_region(timed, dist, dev) * 1e3 / args.steps
             sync_every[0] = False
     eager_ms = None
-    if (plan_graph or training) and not args.no_op_profile:
+    if args.full and (plan_graph or training) and not args.no_op_profile:
         # (training: the timed region is the plain product path as well; forward AND gradient-plan launches are timed here)
         model.denoise_fn.op_profile = prof
         ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -663,7 +719,7 @@ def run_workload(args, env):
     # the same step with the tile GEMMs / 1x1 layers on the f32 MFMA (UNetModel.gemm_bf3 = False): a driver-timed number for a reader who
     # does not accept the bf16x3 emulation as fp32 arithmetic (5 steps after 2 warm-ups, outside the timed region)
     f32mfma_ms = None
-    if args.workload == "c2" and not training and world == 1 and not args.no_f32mfma and model.denoise_fn.gemm_bf3:
+    if args.full and args.workload == "c2" and not training and world == 1 and not args.no_f32mfma and model.denoise_fn.gemm_bf3:
         model.denoise_fn.gemm_bf3 = False
         try:
             for i in range(2):
@@ -686,7 +742,7 @@ def run_workload(args, env):
     # ... and on round 4's Winograd tiles (UNetModel.winograd = 6: F(6x6, 3x3) instead of F(8x8, 3x3) on the large layers -- 7x closer
     # to the reference, ~10 % slower): the same 2 + 5 steps; its parity sample is taken next to the headline's below
     winograd6_ms = None
-    if args.workload in ("c2", "c3") and not training and world == 1 and not args.no_f32mfma and model.denoise_fn.winograd >= 8:
+    if args.full and args.workload in ("c2", "c3") and not training and world == 1 and not args.no_f32mfma and model.denoise_fn.winograd >= 8:
         model.denoise_fn.winograd = 6
         try:
             for i in range(2):
@@ -707,7 +763,7 @@ def run_workload(args, env):
 
     # ... and on round 5's planes (UNetModel.gemm_h2 = False: every tile GEMM on the six-term bf16x3 split): the same 2 + 5 steps
     bf16x3_ms = None
-    if args.workload in ("c2", "c3") and not training and world == 1 and not args.no_f32mfma and model.denoise_fn.gemm_h2:
+    if args.full and args.workload in ("c2", "c3") and not training and world == 1 and not args.no_f32mfma and model.denoise_fn.gemm_h2:
         model.denoise_fn.gemm_h2 = False
         try:
             for i in range(2):
@@ -729,7 +785,7 @@ def run_workload(args, env):
     # c4: the same micro-steps with the training plan on the tiles it had before F(8x8, 3x3) got its gradient side
     # (UNetModel.winograd_train8 = 0: m <= 6 forward, data gradient and weight gradient): one accumulation cycle to build and warm the
     # second plan, then two cycles timed, outside the timed region
-    if training and world == 1 and not args.no_f32mfma and model.denoise_fn.winograd_train8 and model.denoise_fn.winograd >= 8:
+    if args.full and training and world == 1 and not args.no_f32mfma and model.denoise_fn.winograd_train8 and model.denoise_fn.winograd >= 8:
         keep8 = model.denoise_fn.winograd_train8
         model.denoise_fn.winograd_train8 = 0
         try:
@@ -750,6 +806,32 @@ def run_workload(args, env):
         for k in list(model.denoise_fn._plans)[1:]:
             del model.denoise_fn._plans[k]
         torch.cuda.empty_cache()
+
+    ms_per_step = elapsed * 1e3 / args.steps
+    devices = dist_utils.gather_device_info(dist, dev)          # per-rank device ids (+ RCCL version when world > 1)
+    steps_per_s_job = dist_utils.aggregate_throughput(args.steps, elapsed, world)
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "denoise-UNet sampling steps/sec (one step = p_sample of the whole local batch: UNet forward + "
+                      "Brownian-Bridge update) at 256x256 pixel-space BBDM" if args.workload == "c2" else
+                      ("training micro-steps/sec (c4: forward + backward; fused Adam + EMA every accumulate_grad_batches-th)" if training else
+                       f"denoise-UNet sampling steps/sec ({args.workload})"),
+            "value": steps_per_s_job, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": _dtype(next(iter(model.denoise_fn._plans.values())), training),
+            "data": "synthetic (seed 1234 image pairs, random-init weights N(0,0.02))",
+            "config": {"workload": desc, "batch_per_gpu": batch, "image_size": size, "unet_params_M": nparams / 1e6,
+                       "schedule_steps": nsteps_table, "parallelism": f"dp{world} (independent image-pair shards)"},
+            "devices": devices,
+            "hip_graph": bool(plan_graph), "prime_steps": prime,
+            "steps_per_sec_per_gpu": args.steps / elapsed,
+            "img_steps_per_sec": steps_per_s_job * batch,
+            "imgs_per_sec_whole_job": steps_per_s_job * batch / nsteps_table,
+            "training": training_info,
+        }
+    if not args.full:               # the plain run: the headline figure only
+        return line
 
     # ---- per-kernel accounting from the HIP events recorded inside the timed region -------------------------
     by = {}
@@ -963,35 +1045,12 @@ def run_workload(args, env):
             alg_n += 1
     if traffic is not None and alg_n:
         traffic["algorithmic_bytes_per_launch"] = alg_bytes / alg_n
-    ms_per_step = elapsed * 1e3 / args.steps
-    devices = dist_utils.gather_device_info(dist, dev)          # per-rank device ids (+ RCCL version when world > 1)
-    steps_per_s_job = dist_utils.aggregate_throughput(args.steps, elapsed, world)
-
     if rank == 0:
-        line = {
-            "metric": "denoise-UNet sampling steps/sec (one step = p_sample of the whole local batch: UNet forward + "
-                      "Brownian-Bridge update) at 256x256 pixel-space BBDM" if args.workload == "c2" else
-                      ("training micro-steps/sec (c4: forward + backward; fused Adam + EMA every accumulate_grad_batches-th)" if training else
-                       f"denoise-UNet sampling steps/sec ({args.workload})"),
-            "value": steps_per_s_job, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": ("f32 (tile GEMMs: fp32 operands as two fp16 planes under a provable power-of-two scale, 3 fp16-MFMA terms, fp32 "
-                      "accumulate -- measured against fp64 MORE accurate than the six-term bf16x3 split and than the f32 MFMA; 1x1 layers "
-                      "(skip / qkv / proj_out) and the long-sequence attention: the same pair; short-sequence, cross- and training "
-                      "attention: bf16x3; all other kernels native fp32)") if (use_bf3 and terms == 3.0) else
-                     ("f32 (tile GEMMs: fp32 operands split exactly into 3 bf16, 6 bf16-MFMA terms, fp32 accumulate -- fp32-accurate; "
-                      "all other kernels native fp32)") if use_bf3 else "f32", "data": "synthetic (seed 1234 image pairs, random-init weights N(0,0.02))",
-            "config": {"workload": desc, "batch_per_gpu": batch, "image_size": size, "unet_params_M": nparams / 1e6,
-                       "schedule_steps": nsteps_table, "parallelism": f"dp{world} (independent image-pair shards)"},
-            "devices": devices,
-            "hip_graph": bool(plan_graph), "prime_steps": prime,
+        line.update({
             # hip_graph: the timed region replays the forward as ONE hipGraph (the product path); the per-launch HIP events behind
             # `roofline` / `kernel_ms_per_step` then come from a second, eager pass of the same K steps right after it, whose own
             # step time (launch by launch, with two event records around every launch) is eager_profiled_ms_per_step
             "eager_profiled_ms_per_step": eager_ms,
-            "steps_per_sec_per_gpu": args.steps / elapsed,
-            "img_steps_per_sec": steps_per_s_job * batch,
-            "imgs_per_sec_whole_job": steps_per_s_job * batch / nsteps_table,
             "tflops_algorithmic": total_flops_per_step / (ms_per_step * 1e-3) / 1e12,
             "tflops_executed": executed_flops_per_step / (ms_per_step * 1e-3) / 1e12,
             "roofline": {"bound": "mfma", "kernel": dom_name, "achieved": achieved,
@@ -1032,8 +1091,7 @@ def run_workload(args, env):
             "f32mfma_ms_per_step": f32mfma_ms,
             "winograd6_ms_per_step": winograd6_ms,
             "bf16x3_ms_per_step": bf16x3_ms,
-            "training": training_info,
-        }
+        })
         if args.workload in FIRST_STAGE and not args.no_pipeline:
             line["pipeline"] = first_stage_pipeline(args.workload, batch, dev, ms_per_step, nsteps_table)
         # parity sample (every workload, world 1, unless --no-parity): one more p_sample of the SAME batch with known step noise

@@ -1,20 +1,12 @@
 """Shared bodies of the optimizer / EMA parity tests (run on the GPU by test_optim_gpu.py and on the CPU-emulated kernels
-by test_optim_emu_cpu.py): bbdm_amd.optim against torch.optim.Adam and the reference's own EMA class."""
-import os
-import sys
-
+by test_optim_emu_cpu.py): bbdm_amd.optim against torch.optim.Adam and the reference's EMA class (restated)."""
 import pytest
 import torch
 import torch.nn as nn
 
 
 def reference_ema_class():
-    if os.path.isdir("/root/reference/runners/base"):
-        sys.path.insert(0, "/root/reference")
-        from runners.base.EMA import EMA
-        return EMA
-
-    class EMA:                                   # runners/base/EMA.py:4-29
+    class EMA:                                   # the reference's runners/base/EMA.py:4-43, restated
         def __init__(self, ema_decay):
             self.ema_decay, self.backup, self.shadow = ema_decay, {}, {}
 
@@ -31,6 +23,18 @@ def reference_ema_class():
                     else:
                         new_average = param.data
                     self.shadow[name] = new_average.clone()
+
+        def apply_shadow(self, model):
+            for name, param in model.named_parameters():
+                if param.requires_grad:
+                    self.backup[name] = param.data
+                    param.data = self.shadow[name]
+
+        def restore(self, model):
+            for name, param in model.named_parameters():
+                if param.requires_grad:
+                    param.data = self.backup[name]
+            self.backup = {}
     return EMA
 
 

@@ -1,14 +1,15 @@
 """``bbdm_amd.cond_stage.SpatialRescaler`` (condition_key 'SpatialRescaler'): same outputs, state_dict and gradients as the
-reference's class (model/BrownianBridge/base/modules/encoders/modules.py:106-134) when the checkout is mounted; its contract
-without it."""
-import importlib
-import sys
+reference's class (model/BrownianBridge/base/modules/encoders/modules.py:106-134; its outputs are stored in
+tests/golden/ref_parity.pt by oracle/make_golden_refparity.py) and its contract."""
+import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from bbdm_amd.cond_stage import SpatialRescaler
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_parity.pt")
 
 CASES = [dict(n_stages=1, method="bilinear", multiplier=0.5, in_channels=3, out_channels=None, bias=False),
          dict(n_stages=2, method="nearest", multiplier=0.5, in_channels=3, out_channels=8, bias=True),
@@ -37,21 +38,13 @@ def test_contract(kw):
         SpatialRescaler(method="lanczos")
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("kw", CASES)
 def test_matches_the_reference_class(kw):
-    if "/root/reference" not in sys.path:
-        sys.path.insert(0, "/root/reference")
-    try:
-        ref_cls = importlib.import_module("model.BrownianBridge.base.modules.encoders.modules").SpatialRescaler
-    except Exception as e:                                  # the module imports optional packages (transformers, kornia, clip ...)
-        pytest.skip(f"reference encoders module not importable here: {e!r}")
-    torch.manual_seed(1)
-    ref = ref_cls(**kw)
+    ref = next(r for r in torch.load(GOLDEN, weights_only=False)["cond_stage"] if r["kw"] == kw)
     m = SpatialRescaler(**kw)
-    m.load_state_dict(ref.state_dict(), strict=True)
-    x = torch.randn(2, kw["in_channels"], 16, 24)
-    assert torch.equal(m(x), ref(x)) and torch.equal(m.encode(x), ref.encode(x))
+    m.load_state_dict(ref["state_dict"], strict=True)
+    x = ref["x"]
+    assert torch.equal(m(x), ref["fwd"]) and torch.equal(m.encode(x), ref["enc"])
 
 
 def test_latent_model_builds_its_own_rescaler_and_trains_it():

@@ -1,5 +1,5 @@
 """bbdm_amd.optim (fused Adam + EMA) on the CPU-emulated kernels: parity with torch.optim.Adam and with
-the reference's own EMA class (imported from /root/reference when mounted, else an inline restatement of its 8 lines)."""
+the reference's EMA class (an inline restatement of its 8 lines: tests/optim_cases.py)."""
 import pytest
 import torch
 

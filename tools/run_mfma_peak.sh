@@ -20,7 +20,7 @@ smi > $O/smi_mfma_burst.txt & SMI=$!
 ./tools/microbench/mfma_peak burst 3 > $O/mfma_burst.txt 2>&1
 kill $SMI
 smi > $O/smi_bench_c2.txt & SMI=$!
-python bench.py --steps 20 --warmup 5 --no-cpu --no-parity --no-f32mfma --no-extras > $O/bench_c2.json 2> $O/bench_c2.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu --no-parity --no-f32mfma --no-extras > $O/bench_c2.json 2> $O/bench_c2.err
 kill $SMI
 cat $O/mfma_peak.txt $O/mfma_burst.txt
 python - <<P

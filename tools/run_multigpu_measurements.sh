@@ -18,8 +18,8 @@ mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 python -m pytest tests/test_dist_gpu.py -x -q -m gpu > $O/pytest_dist_gpu.txt 2>&1; tail -3 $O/pytest_dist_gpu.txt
 for N in 1 2 4 8; do
-    python bench.py --gpus $N --steps 20 --warmup 5 --no-extras --no-cpu --no-f32mfma > $O/scale_c2_n$N.json 2> $O/scale_c2_n$N.err
-    python bench.py --gpus $N --workload c4 --steps 8 --warmup 1 --no-cpu > $O/scale_c4_n$N.json 2> $O/scale_c4_n$N.err
+    python bench.py --full --gpus $N --steps 20 --warmup 5 --no-extras --no-cpu --no-f32mfma > $O/scale_c2_n$N.json 2> $O/scale_c2_n$N.err
+    python bench.py --full --gpus $N --workload c4 --steps 8 --warmup 1 --no-cpu > $O/scale_c4_n$N.json 2> $O/scale_c4_n$N.err
 done
 python - <<P
 import json

@@ -8,8 +8,8 @@ R=$GRAFT_REPO_ROOT
 TAG=${1:-r05}
 O=gpurun_out/$TAG
 mkdir -p $O
-C3="--set hip_graph=0 --workload c3 --steps 1 --warmup 1 --no-cpu --no-parity --no-f32mfma --no-pipeline --no-op-profile"
-C4="--workload c4 --steps 4 --warmup 0 --no-cpu --no-parity --no-f32mfma --no-op-profile"
+C3="--full --set hip_graph=0 --workload c3 --steps 1 --warmup 1 --no-cpu --no-parity --no-f32mfma --no-pipeline --no-op-profile"
+C4="--full --workload c4 --steps 4 --warmup 0 --no-cpu --no-parity --no-f32mfma --no-op-profile"
 for w in c3 c4; do
   if [ $w = c3 ]; then A="$C3"; else A="$C4"; fi
   ( cd /tmp && timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $R/$O/pmc_fetch_$w -o pmc -- python $R/bench.py $A > $R/$O/pmc_fetch_$w.log 2>&1 )
