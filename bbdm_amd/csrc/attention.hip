@@ -43,8 +43,10 @@ constexpr float LOG2E = 1.44269504088896340736f, LN2 = 0.69314718055994530942f;
 // Now the split + LDS stores of tile t + 1 are dealt between the 24 Q K^T MFMAs of tile t (one stage of 3 - 8 instructions behind each
 // MFMA, fenced with sched_barrier), K / V of tile t + 2 are requested right behind them into the same registers (they land under the
 // softmax and the P V product), and the P split of the second key half is dealt between the first MFMAs of the first half's P V.  Same arithmetic, same bits (tests: attention with option "attn_pipe" 0 / 1).
+// CH = 128: the bf16x3 K / V stages come to 102 KB (two stages of 2 x 3 x 8.5 KB), so one workgroup per CU; the Q planes alone take 96
+// VGPRs and O^T 64 -- launch bounds of one workgroup leave the wave the whole register file (no scratch).
 template <int CH, bool BQ, bool BV, int NW, bool PIPE = false>
-__global__ void __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) attn_fwd_kernel(const float* __restrict__ qsrc, int ldq, int hsq,
+__global__ void __launch_bounds__(NW * 64, CH == 128 ? 1 : (NW == 4 ? 3 : 2)) attn_fwd_kernel(const float* __restrict__ qsrc, int ldq, int hsq,
                                                        const float* __restrict__ ksrc, const float* __restrict__ vsrc, int ldkv,
                                                        int hskv, float* __restrict__ out, int ldo, float* __restrict__ lse,
                                                        int Tq, int T, int heads, int nheads_total, float qscale, float scale) {
@@ -478,8 +480,9 @@ __global__ void __launch_bounds__(256) attn_kv_planes_kernel(const float* __rest
 // (0, 1] is split under ITS exact bound 1 (P 2^14 = h1 + h2); O accumulates P 2^14 V 2^e and is re-scaled once in the epilogue.  The term
 // order is gemm_bf3p.hip's (h1 k2) (h1 k1) (h2 k1).
 constexpr int H2_TA[3] = {0, 0, 1}, H2_TB[3] = {1, 0, 0};
+// CH = 128: 96 KB (NP = 3) / 64 KB (NP = 2) of stages, one / two workgroups per CU.
 template <int CH, int NP = 3>
-__global__ void __launch_bounds__(256, NP == 2 ? 4 : 3) attn_fwd_planes_kernel(const float* __restrict__ qsrc, int ldq, int hsq,
+__global__ void __launch_bounds__(256, CH == 128 ? (NP == 2 ? 2 : 1) : (NP == 2 ? 4 : 3)) attn_fwd_planes_kernel(const float* __restrict__ qsrc, int ldq, int hsq,
                                                                   const unsigned char* __restrict__ planes, float* __restrict__ out, int ldo,
                                                                   float* __restrict__ lse, int T, int heads, int nheads_total, float qscale,
                                                                   const float* __restrict__ bound) {
@@ -698,7 +701,8 @@ static int launch_attention(const float* q, int ldq, int hsq, const float* k, co
 #define BBDM_ATTN_FWD_P(CH)                                                                                                  \
     hipLaunchKernelGGL((attn_fwd_kernel<CH, true, true, 4, true>), grid, dim3(4 * 64), 0, st, q, ldq, hsq, k, v, ldkv, hskv, out, ldo, \
                        lse, Tq, Tk, heads, nht, qscale, kscale)
-    if (ch == 64) { if (bq == 1 && pipe) BBDM_ATTN_FWD_P(64); else if (bq == 1) BBDM_ATTN_FWD_NW(64, true, true); else if (bq) BBDM_ATTN_FWD_NW(64, true, false); else BBDM_ATTN_FWD_NW(64, false, false); }
+    if (ch == 128) { if (bq == 1 && pipe) BBDM_ATTN_FWD_P(128); else if (bq == 1) BBDM_ATTN_FWD_NW(128, true, true); else if (bq) BBDM_ATTN_FWD_NW(128, true, false); else BBDM_ATTN_FWD_NW(128, false, false); }
+    else if (ch == 64) { if (bq == 1 && pipe) BBDM_ATTN_FWD_P(64); else if (bq == 1) BBDM_ATTN_FWD_NW(64, true, true); else if (bq) BBDM_ATTN_FWD_NW(64, true, false); else BBDM_ATTN_FWD_NW(64, false, false); }
     else if (ch == 32) { if (bq == 1 && pipe) BBDM_ATTN_FWD_P(32); else if (bq == 1) BBDM_ATTN_FWD_NW(32, true, true); else if (bq) BBDM_ATTN_FWD_NW(32, true, false); else BBDM_ATTN_FWD_NW(32, false, false); }
 #undef BBDM_ATTN_FWD_P
     else { if (bq) BBDM_ATTN_FWD_NW(16, true, false); else BBDM_ATTN_FWD_NW(16, false, false); }
@@ -711,7 +715,7 @@ extern "C" int bbdm_attention_f32(const float* qkv, int ldq, float* out, int ldo
                                   int ch, int new_order, void* stream) {
     BBDM_REQUIRE(qkv && out, "attention: null pointer");
     BBDM_REQUIRE(N > 0 && T > 0 && heads > 0, "attention: bad shape");
-    BBDM_REQUIRE(ch == 16 || ch == 32 || ch == 64, "attention: head channels %d unsupported (16, 32, 64)", ch);
+    BBDM_REQUIRE(ch == 16 || ch == 32 || ch == 64 || ch == 128, "attention: head channels %d unsupported (16, 32, 64, 128)", ch);
     BBDM_REQUIRE(ldq % 4 == 0 && ldq >= 3 * heads * ch && ldo >= heads * ch && ((uintptr_t)qkv & 15) == 0,
                  "attention: bad pitch / alignment");
     const float scale = 1.0f / sqrtf(sqrtf((float)ch));
@@ -728,7 +732,7 @@ extern "C" int bbdm_attention_f32(const float* qkv, int ldq, float* out, int ldo
 
 // ---- the pre-split form (see attn_kv_planes_kernel): a launch that writes the K / V operand planes of every (image, head) and an
 // attention launch that reads them.  bbdm_attention_kv_planes_bytes returns 0 where the form does not apply (head channels other than
-// 64 / 32, T not a multiple of 128, sequences too short for the extra launch to pay); the results equal bbdm_attention_f32's bit for bit.
+// 128 / 64 / 32, T not a multiple of 128, sequences too short for the extra launch to pay); the results equal bbdm_attention_f32's bit for bit.
 static size_t attn_planes_units(int ch, int np) { return (size_t)(np * (ch / 16) + 2 * np * (ch / 32)); }
 static size_t attn_planes_lds(int ch, int np) {
     const size_t stages = 2 * attn_planes_units(ch, np) * 1024, epilogue = 128 * (size_t)(ch + 1) * 4;
@@ -736,7 +740,7 @@ static size_t attn_planes_lds(int ch, int np) {
 }
 static bool attn_planes_ok(int N, int T, int heads, int ch) {
     const int mode = bbdm_option(BBDM_OPT_ATTN_PIPE);               // 2: long sequences, 3: every shape the layout takes (tests)
-    return (ch == 64 || ch == 32) && T % 128 == 0 && (T >= 1024 || mode >= 3) && bbdm_option(BBDM_OPT_ATTN_BF3) == 1 && mode >= 2;
+    return (ch == 128 || ch == 64 || ch == 32) && T % 128 == 0 && (T >= 1024 || mode >= 3) && bbdm_option(BBDM_OPT_ATTN_BF3) == 1 && mode >= 2;
 }
 extern "C" size_t bbdm_attention_kv_planes_bytes(int N, int T, int heads, int ch) {
     if (N <= 0 || T <= 0 || heads <= 0 || !attn_planes_ok(N, T, heads, ch)) return 0;
@@ -761,7 +765,8 @@ static int attn_kv_planes(const float* qkv, int ldq, void* planes, size_t planes
     const int hs = new_order ? ch : 3 * ch;
     const dim3 grid((unsigned)(N * heads * (T / 32)));
 #define BBDM_ATTN_KV(CH, NP) hipLaunchKernelGGL((attn_kv_planes_kernel<CH, NP>), grid, dim3(256), 0, (hipStream_t)stream, k, v, ldq, hs, (unsigned char*)planes, T, heads, scale, bound)
-    if (ch == 64) { if (bound) BBDM_ATTN_KV(64, 2); else BBDM_ATTN_KV(64, 3); }
+    if (ch == 128) { if (bound) BBDM_ATTN_KV(128, 2); else BBDM_ATTN_KV(128, 3); }
+    else if (ch == 64) { if (bound) BBDM_ATTN_KV(64, 2); else BBDM_ATTN_KV(64, 3); }
     else { if (bound) BBDM_ATTN_KV(32, 2); else BBDM_ATTN_KV(32, 3); }
 #undef BBDM_ATTN_KV
     BBDM_CHECK_LAUNCH("attention_kv_planes");
@@ -778,7 +783,20 @@ static int attn_planes(const float* qkv, int ldq, float* out, int ldo, float* ls
     const dim3 grid((unsigned)(8ll * ((nht + 7) / 8) * qblocks));
     const int hsq = new_order ? ch : 3 * ch;
 #define BBDM_ATTN_PL(CH, NP) hipLaunchKernelGGL((attn_fwd_planes_kernel<CH, NP>), grid, dim3(256), attn_planes_lds(CH, NP), (hipStream_t)stream, qkv, ldq, hsq, (const unsigned char*)planes, out, ldo, lse, T, heads, nht, scale, bound)
-    if (ch == 64) { if (bound) BBDM_ATTN_PL(64, 2); else BBDM_ATTN_PL(64, 3); }
+    if (ch == 128) {         // 96 / 64 KB of dynamic LDS: above the default limit, raised once per device
+        static bool lds_set_dev[BBDM_MAX_DEVICES] = {};
+        bool& lds_set = lds_set_dev[bbdm_device_slot()];
+        if (!lds_set) {
+            BBDM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_planes_kernel<128, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)attn_planes_lds(128, 3)) == hipSuccess &&
+                             hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_planes_kernel<128, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)attn_planes_lds(128, 2)) == hipSuccess,
+                         "attention_planes: hipFuncSetAttribute(%zu B LDS) failed", attn_planes_lds(128, 3));
+            lds_set = true;
+        }
+        if (bound) BBDM_ATTN_PL(128, 2); else BBDM_ATTN_PL(128, 3);
+    }
+    else if (ch == 64) { if (bound) BBDM_ATTN_PL(64, 2); else BBDM_ATTN_PL(64, 3); }
     else { if (bound) BBDM_ATTN_PL(32, 2); else BBDM_ATTN_PL(32, 3); }
 #undef BBDM_ATTN_PL
     BBDM_CHECK_LAUNCH("attention_planes");
@@ -811,7 +829,7 @@ extern "C" int bbdm_cross_attention_f32(const float* q, int ldq, const float* k,
                                         float* lse, int N, int Tq, int Tk, int heads, int ch, void* stream) {
     BBDM_REQUIRE(q && k && v && out, "cross_attention: null pointer");
     BBDM_REQUIRE(N > 0 && Tq > 0 && Tk > 0 && heads > 0, "cross_attention: bad shape");
-    BBDM_REQUIRE(ch == 16 || ch == 32 || ch == 64, "cross_attention: head channels %d unsupported (16, 32, 64)", ch);
+    BBDM_REQUIRE(ch == 16 || ch == 32 || ch == 64 || ch == 128, "cross_attention: head channels %d unsupported (16, 32, 64, 128)", ch);
     BBDM_REQUIRE(ldq % 4 == 0 && ldkv % 4 == 0 && ldq >= heads * ch && ldkv >= heads * ch && ldo >= heads * ch &&
                      (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0,
                  "cross_attention: bad pitch / alignment");

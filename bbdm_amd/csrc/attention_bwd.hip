@@ -346,7 +346,7 @@ int attention_bwd_common(const float* q, int ldq, int hsq, const float* k, const
     hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(pb), dim3(256), 0, st, out, ldo, dout, lddo, dwork, N, Tq, heads, ch);
 #define BBDM_ATTN_BWD(CH) \
     launch_bwd<CH>(q, ldq, hsq, k, v, ldkv, hskv, dout, lddo, lse, dwork, dq, lddq, dk, dv, lddkv, N, Tq, Tk, heads, qscale, kscale, st)
-    if (ch == 64) BBDM_ATTN_BWD(64); else if (ch == 32) BBDM_ATTN_BWD(32); else BBDM_ATTN_BWD(16);
+    if (ch == 128) BBDM_ATTN_BWD(128); else if (ch == 64) BBDM_ATTN_BWD(64); else if (ch == 32) BBDM_ATTN_BWD(32); else BBDM_ATTN_BWD(16);
 #undef BBDM_ATTN_BWD
     return 0;
 }
@@ -357,7 +357,7 @@ extern "C" int bbdm_attention_bwd_f32(const float* qkv, int ldq, const float* ou
                                       const float* lse, float* dwork, float* dqkv, int lddq, int N, int T, int heads, int ch,
                                       int new_order, void* stream) {
     BBDM_REQUIRE(qkv && out && dout && lse && dwork && dqkv, "attention_bwd: null pointer");
-    BBDM_REQUIRE(N > 0 && T > 0 && heads > 0 && (ch == 16 || ch == 32 || ch == 64), "attention_bwd: bad shape (ch=%d)", ch);
+    BBDM_REQUIRE(N > 0 && T > 0 && heads > 0 && (ch == 16 || ch == 32 || ch == 64 || ch == 128), "attention_bwd: bad shape (ch=%d)", ch);
     BBDM_REQUIRE(ldq % 4 == 0 && lddo % 4 == 0 && ldo % 4 == 0 && ldq >= 3 * heads * ch && lddq >= 3 * heads * ch &&
                      ldo >= heads * ch && lddo >= heads * ch,
                  "attention_bwd: bad pitch");
@@ -380,7 +380,7 @@ extern "C" int bbdm_cross_attention_bwd_f32(const float* q, int ldq, const float
                                             int lddq, float* dk, float* dv, int lddkv, int N, int Tq, int Tk, int heads, int ch,
                                             void* stream) {
     BBDM_REQUIRE(q && k && v && out && dout && lse && dwork && dq && dk && dv, "cross_attention_bwd: null pointer");
-    BBDM_REQUIRE(N > 0 && Tq > 0 && Tk > 0 && heads > 0 && (ch == 16 || ch == 32 || ch == 64),
+    BBDM_REQUIRE(N > 0 && Tq > 0 && Tk > 0 && heads > 0 && (ch == 16 || ch == 32 || ch == 64 || ch == 128),
                  "cross_attention_bwd: bad shape (ch=%d)", ch);
     const int C = heads * ch;
     BBDM_REQUIRE(ldq % 4 == 0 && ldkv % 4 == 0 && lddo % 4 == 0 && ldo % 4 == 0 && ldq >= C && ldkv >= C && ldo >= C && lddo >= C &&

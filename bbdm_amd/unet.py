@@ -764,9 +764,9 @@ class UNetModel(nn.Module):
             # the SpatialTransformer's head width is ch // heads
             nh = num_heads if num_head_channels == -1 else ch // num_head_channels
             d_head = ch // nh
-            if d_head not in (16, 32, 64):
+            if d_head not in (16, 32, 64, 128):
                 raise NotImplementedError(f"bbdm_amd.UNetModel: SpatialTransformer head width {d_head} (channels {ch} / "
-                                          f"{nh} heads) is not implemented; the attention kernel takes 16, 32 or 64")
+                                          f"{nh} heads) is not implemented; the attention kernel takes 16, 32, 64 or 128")
             return SpatialTransformer(ch, nh, d_head, depth=transformer_depth, context_dim=context_dim)
 
         # construction order == openaimodel.py:518-691 (keeps RNG consumption, hence seeded init, identical)

@@ -241,7 +241,7 @@ int bbdm_groupnorm_apply_f32(const float* x, int ldx, const bbdm_stats_t* stats,
 /* qkv: NHWC [N, T, 3*heads*ch] pitch ldq.  Channel of (head h, part p in {q,k,v}, c):
  *   legacy (new_order = 0): h*3*ch + p*ch + c        new order: p*heads*ch + h*ch + c
  * out: NHWC [N, T, heads*ch] pitch ldo, channel h*ch + c.  softmax((q*s)^T (k*s)) v with s = ch^-1/4,
- * streamed over keys (no T x T tensor is ever materialised).  ch in {16, 32, 64}.
+ * streamed over keys (no T x T tensor is ever materialised).  ch in {16, 32, 64, 128}.
  * lse (may be NULL): fp32 [N][heads][T] log-sum-exp of every query's score row, kept for the backward pass. */
 int bbdm_attention_f32(const float* qkv, int ldq, float* out, int ldo, float* lse, int N, int T, int heads, int ch,
                        int new_order, void* stream);
@@ -249,7 +249,7 @@ int bbdm_attention_f32(const float* qkv, int ldq, float* out, int ldo, float* ls
  * every (image, head)'s keys and values ONCE (K scaled; 6 bytes per element in the MFMA fragment order, csrc/attention.hip) and
  * bbdm_attention_planes_f32 copies them tile by tile into LDS (LDS-DMA) instead of splitting K / V again in each of the T / 128
  * workgroups that walk them.  bbdm_attention_kv_planes_bytes: size of `planes`, or 0 where the form does not apply (ch not in
- * {32, 64}, T % 128 != 0, T < 1024, option "attn_pipe" < 2) -- callers then use bbdm_attention_f32.  Bit-equal to it. */
+ * {32, 64, 128}, T % 128 != 0, T < 1024, option "attn_pipe" < 2) -- callers then use bbdm_attention_f32.  Bit-equal to it. */
 size_t bbdm_attention_kv_planes_bytes(int N, int T, int heads, int ch);
 int bbdm_attention_kv_planes_f32(const float* qkv, int ldq, void* planes, size_t planes_bytes, int N, int T, int heads, int ch,
                                  int new_order, void* stream);
@@ -271,7 +271,7 @@ int bbdm_h2_rowl1_f32(const float* w, const float* bias, int rows, int cols, flo
 int bbdm_h2_affine_bound_f32(const float* in_bound, const float* gain2, float* out_bound, void* stream);
 /* Backward of the above (training; the reference re-runs the block under CheckpointFunction, util.py:119-148):
  * dqkv (same layout / pitch convention as qkv, pitch lddq) from dout [N,T,heads*ch] (pitch lddo), the forward's
- * qkv, out and lse.  Two streaming kernels (dQ per query block; dK,dV per key block), no T x T tensor. */
+ * qkv, out and lse.  Two streaming kernels (dQ per query block; dK,dV per key block), no T x T tensor.  ch in {16, 32, 64, 128}. */
 int bbdm_attention_bwd_f32(const float* qkv, int ldq, const float* out, int ldo, const float* dout, int lddo,
                            const float* lse, float* dwork /* N*heads*T floats */, float* dqkv, int lddq,
                            int N, int T, int heads, int ch, int new_order, void* stream);
@@ -375,7 +375,7 @@ int bbdm_vq_nearest_f32(const float* z, int ldz, const float* codebook, long lon
  *      modules/attention.py) -------------------------------------------------------------------------------------------- */
 /* CrossAttention.forward (attention.py:170-194): out[n, i, h*ch + d] = sum_j softmax_j(q_i . k_j * ch^-1/2) v_j per head.
  * q: [N][Tq][ldq], k / v: [N][Tk][ldkv] token-major ('b n (h d)': head h at channel h*ch), out: [N][Tq][ldo].
- * ch in {16, 32, 64}.  Streaming softmax on the f32 matrix core, same kernel as bbdm_attention_f32.
+ * ch in {16, 32, 64, 128}.  Streaming softmax on the f32 matrix core, same kernel as bbdm_attention_f32.
  * lse (may be NULL): [N][heads][Tq] log-sum-exp of the scaled scores, kept for the backward pass.
  * bbdm_cross_attention_bwd_f32 (autograd of the above; the reference re-runs the block under CheckpointFunction,
  * attention.py:212-213): dq [N][Tq] (pitch lddq), dk / dv [N][Tk] (pitch lddkv), overwritten; dwork: N*heads*Tq floats. */

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """The C2 attention (N 16, T 4096, 16 heads x 64) on bbdm_attention_f32, on the pre-split pair (K / V planes + attention) and on the pair's
-fp16-plane form (round 6), HIP events.
-    python tools/attn_bench.py [--reps 20]"""
+fp16-plane form (round 6), HIP events.  --shape N,T,heads,ch takes any width the kernels take (16, 32, 64, 128); --bwd adds the
+training pair (forward with the log-sum-exp + bbdm_attention_bwd_f32).
+    python tools/attn_bench.py [--reps 20] [--shape 16,4096,8,128] [--bwd]"""
 import argparse
 import os
 import sys
@@ -17,6 +18,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--shape", default="16,4096,16,64")
+    ap.add_argument("--bwd", action="store_true", help="also time the forward with lse + the backward (training)")
     args = ap.parse_args()
     N, T, heads, ch = (int(v) for v in args.shape.split(","))
     dev = torch.device("cuda:0")
@@ -43,6 +45,15 @@ def main():
     one = lambda: _lib.call("bbdm_attention_f32", qkv.data_ptr(), 3 * C, out0.data_ptr(), C, None, N, T, heads, ch, 0, st)
     t0 = timed(one)
     print(f"one launch      : {t0:6.3f} ms  {fl / t0 / 1e9:6.1f} TF/s")
+    if args.bwd:        # S recomputed + dP, dV, dQ, dK: five T x T x ch products
+        lse, work = torch.empty(N * heads * T, device=dev), torch.empty(N * heads * T, device=dev)
+        dout, dqkv = torch.randn(N, T, C, device=dev), torch.empty_like(qkv)
+        fwd = lambda: _lib.call("bbdm_attention_f32", qkv.data_ptr(), 3 * C, out0.data_ptr(), C, lse.data_ptr(), N, T, heads, ch, 0, st)
+        bwd = lambda: _lib.call("bbdm_attention_bwd_f32", qkv.data_ptr(), 3 * C, out0.data_ptr(), C, dout.data_ptr(), C, lse.data_ptr(),
+                                work.data_ptr(), dqkv.data_ptr(), 3 * C, N, T, heads, ch, 0, st)
+        tf, tb = timed(fwd), timed(bwd)
+        print(f"fwd + lse       : {tf:6.3f} ms  {fl / tf / 1e9:6.1f} TF/s")
+        print(f"backward        : {tb:6.3f} ms  {1.25 * fl / tb / 1e9:6.1f} TF/s   fwd + bwd {tf + tb:6.3f} ms")
     if nb:
         kv = lambda: _lib.call("bbdm_attention_kv_planes_f32", qkv.data_ptr(), 3 * C, planes.data_ptr(), nb, N, T, heads, ch, 0, st)
         at = lambda: _lib.call("bbdm_attention_planes_f32", qkv.data_ptr(), 3 * C, out1.data_ptr(), C, None, N, T, heads, ch, 0, planes.data_ptr(), st)
