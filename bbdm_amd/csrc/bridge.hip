@@ -82,6 +82,54 @@ __global__ void p_step_kernel(const float* __restrict__ x_t, const float* __rest
     }
 }
 
+// p_step_kernel with a (step, next step, flag) per image: one image per blockIdx.y, so the coefficients are evaluated once
+// per thread and image.  flag 0: a step with noise, 1: the last step (x_next = x0_recon, no noise read), 2: an inactive slot
+// (nothing read or written).  The float expressions are p_step_kernel's, in the same order: an image whose (t, t_next, last)
+// equals a scalar launch's gets the scalar kernel's bits.
+__global__ void p_step_batched_kernel(const float* __restrict__ x_t, const float* __restrict__ y,
+                                      const float* __restrict__ pred, const float* __restrict__ noise,
+                                      const float* __restrict__ m_tab, const float* __restrict__ var_tab,
+                                      const int64_t* __restrict__ t_arr, const int64_t* __restrict__ t_next_arr,
+                                      const int64_t* __restrict__ flag_arr, float eta, int clip, int objective,
+                                      float* __restrict__ x_next, float* __restrict__ x0_recon,
+                                      float* __restrict__ x_next_alias, int per_sample) {
+    const int n = blockIdx.y;
+    const int64_t flag = flag_arr[n];
+    if (flag == 2) return;
+    const int is_last = flag == 1;
+    const int64_t t = t_arr[n];
+    const float m_t = m_tab[t], var_t = var_tab[t];
+    const float sig_obj = sqrtf(var_t);
+    float m_nt = 0.f, sigma_t = 0.f, coef = 0.f;
+    if (!is_last) {
+        const int64_t t_next = t_next_arr[n];
+        m_nt = m_tab[t_next];
+        const float var_nt = var_tab[t_next];
+        const float a = (1.f - m_t) * (1.f - m_t);
+        const float b = (1.f - m_nt) * (1.f - m_nt);
+        const float sigma2 = (var_t - var_nt * a / b) * var_nt / var_t;
+        sigma_t = sqrtf(sigma2) * eta;
+        coef = sqrtf((var_nt - sigma2) / var_t);
+    }
+    const size_t base = (size_t)n * per_sample;
+    for (size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x; k < (size_t)per_sample; k += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = base + k;
+        const float xt = x_t[i], yy = y[i];
+        float x0r = predict_x0_one(objective, xt, yy, pred[i], m_t, sig_obj);
+        if (clip) x0r = fminf(fmaxf(x0r, -1.f), 1.f);
+        x0_recon[i] = x0r;
+        if (is_last) {
+            x_next[i] = x0r;
+            if (x_next_alias) x_next_alias[i] = x0r;
+        } else {
+            const float mean = (1.f - m_nt) * x0r + m_nt * yy + coef * (xt - (1.f - m_t) * x0r - m_t * yy);
+            const float xn = mean + sigma_t * noise[i];
+            x_next[i] = xn;
+            if (x_next_alias) x_next_alias[i] = xn;
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            unsigned long long* __restrict__ partial, size_t count, int loss_type) {
     __shared__ double red[4];
@@ -181,6 +229,22 @@ extern "C" int bbdm_bb_p_sample_step_f32(const float* x_t, const float* y, const
     hipLaunchKernelGGL(p_step_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x_t, y, pred, noise,
                        m_t, variance_t, t, t_next, is_last, eta, clip, objective, x_next, x0_recon, x_next_alias, total);
     BBDM_CHECK_LAUNCH("p_sample_step");
+    return BBDM_OK;
+}
+
+extern "C" int bbdm_bb_p_sample_step_batched_f32(const float* x_t, const float* y, const float* pred, const float* noise,
+                                                 const float* m_t, const float* variance_t, const int64_t* t,
+                                                 const int64_t* t_next, const int64_t* flag, float eta, int clip, int objective,
+                                                 float* x_next, float* x0_recon, float* x_next_alias, int N, int per_sample,
+                                                 void* stream) {
+    BBDM_REQUIRE(x_t && y && pred && noise && m_t && variance_t && t && t_next && flag && x_next && x0_recon,
+                 "p_sample_step_batched: null pointer");
+    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "p_sample_step_batched: bad args");
+    const size_t b = ((size_t)per_sample + 255) / 256;
+    const unsigned bx = (unsigned)(b > 2048 ? 2048 : b);
+    hipLaunchKernelGGL(p_step_batched_kernel, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x_t, y, pred, noise,
+                       m_t, variance_t, t, t_next, flag, eta, clip, objective, x_next, x0_recon, x_next_alias, per_sample);
+    BBDM_CHECK_LAUNCH("p_sample_step_batched");
     return BBDM_OK;
 }
 

@@ -1,0 +1,253 @@
+"""Continuous-batching bridge sampler: many sampling requests through ONE UNet plan of a fixed width, each image at its own step.
+
+The reference samples a test set by calling ``net.sample(x_cond)`` ``sample_num`` times on every test batch
+(runners/DiffusionBasedModelRunners/BBDMRunner.py:224-253): 200-step loops at batch 8, and a smaller batch at the end of the set.
+``p_sample`` moves a whole batch through one shared step index, so such a batch can be neither widened nor topped up.  Here every slot
+of a ``batch_size``-wide batch carries its own position in ``model.steps``:
+
+* one UNet call per step with the slots' own timesteps (``UNetModel.infer_steps``: one plan, one hipGraph);
+* one launch of ``bbdm_bb_p_sample_step_batched_f32`` (csrc/bridge.hip), the fused update of ``p_sample`` with a step, next step and
+  flag per image -- bit for bit the scalar kernel's result for an image at the same (step, next, last);
+* a request that finishes frees its slot, and the next queued request starts there at ``x_t = y`` (BrownianBridgeModel.py:203-221).
+
+Noise contract: the noise of a request's k-th step with ``steps[i] != 0`` is ``torch.randn(shape, generator=its_generator, device=dev)``
+drawn in step order, and nothing else draws from that generator.  The noise a request receives is therefore independent of its slot,
+its batch-mates and its arrival time.  Its result still depends on its batch-mates through the fp16-pair bounds that the UNet plan takes
+over the batch (within tolerance, not bitwise).  A group of requests submitted together and run in lockstep computes exactly what
+``model.sample`` computes on the same conditions with the same noise.
+"""
+from __future__ import annotations
+
+import collections
+from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
+
+import torch
+
+from .model import BrownianBridgeModel, LatentBrownianBridgeModel, _OBJECTIVES, _f32c, _launch
+from .unet import UNetModel
+
+_STEP, _LAST, _IDLE = 0, 1, 2          # per-slot flags of bbdm_bb_p_sample_step_batched_f32
+
+
+class _Request:
+    __slots__ = ("key", "y", "ctx", "gen")
+
+    def __init__(self, key, y, ctx, gen):
+        self.key, self.y, self.ctx, self.gen = key, y, ctx, gen
+
+
+def _pow2(k: int) -> int:
+    p = 1
+    while p < k:
+        p *= 2
+    return p
+
+
+class BridgeSampler:
+    """``BridgeSampler(model, batch_size, clip_denoised=False)`` for a :class:`BrownianBridgeModel` or
+    :class:`LatentBrownianBridgeModel` in ``eval()``.
+
+    ``submit([(key, x_cond, generator), ...])`` queues a group of requests (``x_cond``: one condition image ``[C, H, W]``); iterating
+    over the sampler runs steps until every queued request has finished and yields ``(key, sample)`` as each one does -- in pixel space
+    (LBBDM: ``decode(latent, cond=False)``).  ``sample_set`` is the ``sample_to_eval``-shaped helper.  All requests share
+    ``model.steps`` and one sample shape."""
+
+    def __init__(self, model: BrownianBridgeModel, batch_size: int, clip_denoised: bool = False):
+        if not isinstance(model, BrownianBridgeModel):
+            raise TypeError("BridgeSampler drives a bbdm_amd BrownianBridgeModel / LatentBrownianBridgeModel")
+        if not isinstance(model.denoise_fn, UNetModel):
+            raise TypeError("BridgeSampler needs the bbdm_amd UNetModel as denoise_fn (per-image timesteps on its plan)")
+        if model.objective not in _OBJECTIVES:
+            raise NotImplementedError
+        if int(batch_size) < 1 or int(batch_size) > 65535:
+            raise ValueError(f"batch_size must be in [1, 65535], got {batch_size}")
+        self.model, self.width, self.clip = model, int(batch_size), bool(clip_denoised)
+        self.latent = isinstance(model, LatentBrownianBridgeModel)
+        self.device = model.m_t.device
+        self._queue: collections.deque = collections.deque()
+        self._slots: List[Optional[list]] = [None] * self.width        # [request, i] per slot: i = its position in model.steps
+        self._shape = None              # (x_t shape per image, context shape per image or None)
+        self._plan = None
+        self._x = self._x_other = self._y = self._ctx = self._noise = self._x0 = None
+
+    # ------------------------------------------------------------------------------------------------------
+    def _check_schedule(self):
+        """The checks of ``p_sample`` (model.py) for every index a request will take, at submission."""
+        m = self.model
+        steps = m._steps_host()
+        for i, step in enumerate(steps):
+            nxt = 0 if step == 0 else steps[i + 1]
+            if not (0 <= step < m.num_timesteps and 0 <= nxt < m.num_timesteps):
+                raise IndexError(f"timestep {max(step, nxt)} is out of range for the {m.num_timesteps}-entry schedule")
+        return steps
+
+    def _condition(self, x_cond: torch.Tensor):
+        """(y, context) of a batch of conditions, as ``p_sample_loop`` / ``LatentBrownianBridgeModel.sample`` form them."""
+        m = self.model
+        if self.latent:
+            y = m.encode(x_cond, cond=True)
+            ctx = m.get_cond_stage_context(x_cond)
+        else:
+            y, ctx = x_cond, None
+        if m.condition_key == "nocond":
+            ctx = None
+        else:
+            ctx = y if ctx is None else ctx
+        return _f32c(y), None if ctx is None else _f32c(ctx)
+
+    def submit(self, requests: Iterable[Tuple[object, torch.Tensor, Optional[torch.Generator]]]):
+        """Queue a group of ``(key, x_cond, generator)``.  The group's distinct conditions go through the first stage and the
+        conditioning stage in ONE call each.  Raises what ``p_sample`` raises for a condition of another shape (RuntimeError) or a
+        schedule it would index out of range (IndexError), before anything is queued."""
+        reqs = list(requests)
+        if not reqs:
+            return
+        self._check_schedule()
+        rows, uniq = [], {}
+        for _, c, _ in reqs:          # requests that pass the same tensor object share its row (sample_set: sample_num draws per condition)
+            if id(c) not in uniq:
+                uniq[id(c)] = len(rows)
+                rows.append(c if c.dim() == 3 else c.reshape(c.shape[-3:]))
+        x_cond = torch.stack([r.to(self.device, torch.float32) for r in rows])
+        with torch.no_grad():
+            y, ctx = self._condition(x_cond)
+        cin = y.shape[1] + (ctx.shape[1] if ctx is not None else 0)
+        if cin != self.model.denoise_fn.in_channels:           # (UNetModel._check_inputs, where p_sample would fail)
+            raise RuntimeError(f"expected {self.model.denoise_fn.in_channels} input channels (x + context), got {cin}")
+        shape = (tuple(y.shape[1:]), None if ctx is None else tuple(ctx.shape[1:]))
+        if self._shape is None:
+            self._allocate(shape)
+        elif shape != self._shape:
+            raise RuntimeError(f"condition of shape {shape} in a sampler of shape {self._shape} (one sample shape per sampler)")
+        for key, c, gen in reqs:
+            r = uniq[id(c)]
+            self._queue.append(_Request(key, y[r], None if ctx is None else ctx[r], gen))
+
+    def _allocate(self, shape):
+        self._shape = shape
+        W, f32 = self.width, dict(dtype=torch.float32, device=self.device)
+        # zeros, not empty: the rows of idle slots still go through the UNet (their output is ignored), and must be finite there
+        self._y = torch.zeros((W,) + shape[0], **f32)
+        self._x = torch.zeros((W,) + shape[0], **f32)
+        self._x_other = torch.zeros((W,) + shape[0], **f32)
+        self._noise = torch.zeros((W,) + shape[0], **f32)
+        self._x0 = torch.zeros((W,) + shape[0], **f32)
+        self._ctx = None if shape[1] is None else torch.zeros((W,) + shape[1], **f32)
+
+    # ------------------------------------------------------------------------------------------------------
+    def busy(self) -> bool:
+        return bool(self._queue) or any(s is not None for s in self._slots)
+
+    def __iter__(self) -> Iterator[Tuple[object, torch.Tensor]]:
+        while self.busy():
+            yield from self.step()
+
+    def _refill(self):
+        """Free slots take the next queued requests, starting at x_t = y.  Only their rows are written: of the sampler's y / x_t /
+        context and -- when the plan holds the sampler's tensors -- of the plan's input buffers, so the UNet call copies nothing."""
+        free = [j for j, s in enumerate(self._slots) if s is None]
+        if not free or not self._queue:
+            return
+        plan = self._plan
+        held_x, held_c = plan.holding(self._x, self._ctx) if plan is not None else (False, False)
+        for j in free:
+            if not self._queue:
+                break
+            req = self._queue.popleft()
+            self._slots[j] = [req, 0]
+            self._y[j].copy_(req.y)
+            self._x[j].copy_(req.y)
+            if held_x:
+                plan.x_in[j].copy_(req.y)
+            if self._ctx is not None:
+                self._ctx[j].copy_(req.ctx)
+                if held_c:
+                    plan.ctx_in[j].copy_(req.ctx)
+        if held_x:
+            plan.holds_input(self._x)
+        if held_c and self._ctx is not None:
+            plan.holds_context(self._ctx)
+
+    @torch.no_grad()
+    def step(self) -> List[Tuple[object, torch.Tensor]]:
+        """One sampler step: refill, one UNet call, the noise of the slots that need it, one bridge launch; returns the requests that
+        finished in it as ``(key, sample)``."""
+        self._refill()
+        live = [j for j, s in enumerate(self._slots) if s is not None]
+        if not live:
+            return []
+        m, W = self.model, self.width
+        steps = m._steps_host()
+        n = len(steps)
+        idx = [[0] * W, [0] * W, [_IDLE] * W]           # step, next step, flag per slot
+        for j in live:
+            i = self._slots[j][1]
+            step = steps[i]
+            idx[0][j] = step
+            if step == 0:
+                idx[2][j] = _LAST
+            else:
+                idx[1][j], idx[2][j] = steps[i + 1], _STEP
+        idx_d = torch.tensor(idx, dtype=torch.int64).to(self.device)
+        pred, plan = m.denoise_fn.infer_steps(self._x, idx_d[0], self._ctx)
+        self._plan = plan
+        for j in live:
+            if idx[2][j] == _STEP:       # == torch.randn(shape, generator=gen, device=dev): randn is empty(...).normal_(0, 1, gen)
+                self._noise[j].normal_(generator=self._slots[j][0].gen)
+        x, xn = self._x, self._x_other
+        _launch(x, "bbdm_bb_p_sample_step_batched_f32", x.data_ptr(), self._y.data_ptr(), pred.data_ptr(), self._noise.data_ptr(),
+                m.m_t.data_ptr(), m.variance_t.data_ptr(), idx_d[0].data_ptr(), idx_d[1].data_ptr(), idx_d[2].data_ptr(),
+                float(m.eta), 1 if self.clip else 0, _OBJECTIVES[m.objective], xn.data_ptr(), self._x0.data_ptr(),
+                plan.x_in.data_ptr(), W, x[0].numel())
+        plan.holds_input(xn)                        # x_in holds x_next (the kernel's second destination): the next call copies nothing
+        self._x, self._x_other = xn, x
+        done = []
+        for j in live:
+            slot = self._slots[j]
+            if slot[1] == n - 1:
+                done.append(j)
+            else:
+                slot[1] += 1
+        out = self._emit(done)
+        for j in done:
+            self._slots[j] = None
+        return out
+
+    def _emit(self, done: Sequence[int]) -> List[Tuple[object, torch.Tensor]]:
+        if not done:
+            return []
+        keys = [self._slots[j][0].key for j in done]
+        if not self.latent:
+            imgs = torch.stack([self._x[j] for j in done])
+        else:
+            # ONE decode call for the slots that finished together, padded to a power of two with copies of its last row: a few plan
+            # shapes for the first stage (a lockstep group of a power-of-two size decodes unpadded, as model.sample does)
+            rows = list(done) + [done[-1]] * (_pow2(len(done)) - len(done))
+            imgs = self.model.decode(torch.stack([self._x[j] for j in rows]), cond=False)[:len(done)]
+        return list(zip(keys, imgs.unbind(0)))
+
+    # ------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample_set(self, conds: torch.Tensor, sample_num: int, seeds: Sequence[int], group: int = 8) -> torch.Tensor:
+        """``sample_to_eval``'s sampling (BBDMRunner.py:224-253) over a whole test set: ``sample_num`` samples of each of the M
+        conditions ``conds`` [M, C, H, W].  Each test batch of ``group`` conditions is submitted as one group; the sample (m, s) draws
+        its noise from a generator on the model's device seeded with ``seeds[m * sample_num + s]``.  Returns [M, sample_num, C, H, W]."""
+        M = conds.shape[0]
+        seeds = [int(s) for s in torch.as_tensor(seeds).reshape(-1).tolist()]
+        if len(seeds) != M * sample_num:
+            raise ValueError(f"sample_set: {len(seeds)} seeds for {M} conditions x {sample_num} samples")
+        for b0 in range(0, M, group):
+            reqs = []
+            for mi in range(b0, min(M, b0 + group)):
+                c = conds[mi]
+                for s in range(sample_num):
+                    g = torch.Generator(device=self.device)
+                    g.manual_seed(seeds[mi * sample_num + s])
+                    reqs.append(((mi, s), c, g))
+            self.submit(reqs)
+        out = None
+        for (mi, s), img in self:
+            if out is None:
+                out = img.new_empty((M, sample_num) + tuple(img.shape))
+            out[mi, s] = img
+        return out

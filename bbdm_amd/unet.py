@@ -934,6 +934,14 @@ class UNetModel(nn.Module):
         plan = self._plan_for(x, training=False)
         return plan.run(x, int(step), ctx, None, True), plan
 
+    @torch.no_grad()
+    def infer_steps(self, x, timesteps: torch.Tensor, context=None):
+        """``infer_step`` with a timestep per image (``timesteps``: int64 [N] on x's device; bbdm_amd.sampler.BridgeSampler, whose
+        slots are at different steps).  The embedding reads the same int64 buffer as ``infer_step`` fills: equal values, equal bits."""
+        x, ctx = self._check_inputs(x, context)
+        plan = self._plan_for(x, training=False)
+        return plan.run(x, timesteps, ctx, None, True), plan
+
     def _check_inputs(self, x, context):
         _lib.require_gpu(x, context)
         if x.dtype != torch.float32:
@@ -2694,6 +2702,18 @@ class _Plan:
         """``x_in`` now holds the value of ``x`` (the fused bridge kernel wrote x_next there as well: csrc/bridge.hip)."""
         v = _ver(x)
         self._x_src = None if isinstance(v, _NoVersion) else (x, v)
+
+    def holding(self, x: torch.Tensor, ctx: Optional[torch.Tensor]):
+        """(whether ``x_in`` holds ``x``, whether ``ctx_in`` holds ``ctx``) -- the test ``run`` makes before it skips a copy."""
+        src, csrc = getattr(self, "_x_src", None), getattr(self, "_ctx_src", None)
+        hx = src is not None and src[0] is x and src[1] == _ver(x)
+        hc = self.ctx_in is None or (ctx is not None and csrc is not None and csrc[0] is ctx and csrc[1] == _ver(ctx))
+        return hx, hc
+
+    def holds_context(self, ctx: torch.Tensor):
+        """``ctx_in`` now holds the value of ``ctx`` (a caller that wrote the changed rows of both: bbdm_amd.sampler's refill)."""
+        v = _ver(ctx)
+        self._ctx_src = None if isinstance(v, _NoVersion) else (ctx, v)
 
     def run(self, x, t, ctx, out=None, borrow=False):
         with _lib.device_guard(self.device):        # NULL-stream launches follow the current device (see _lib.device_guard)

@@ -320,6 +320,16 @@ int bbdm_bb_p_sample_step_f32(const float* x_t, const float* y, const float* pre
                               const float* m_t, const float* variance_t, int t, int t_next, int is_last,
                               float eta, int clip, int objective, float* x_next, float* x0_recon, float* x_next_alias,
                               int N, int per_sample, void* stream);
+/* The same step with a step index per image (continuous batching: bbdm_amd/sampler.py).  Replaces the scalar t / t_next /
+ * is_last of BBM.py:171-201 (and the steps[i]==0 branch :174-180) with device arrays of N: t[n], t_next[n] and flag[n]
+ * (0 a step with noise, 1 the last step: x_next = x0_recon and no noise read, 2 an inactive slot: its rows of x_next,
+ * x0_recon and x_next_alias are neither read nor written).  An image whose (t, t_next, last) equals a scalar launch's gets
+ * bbdm_bb_p_sample_step_f32's bits.  The table indices are not checked here (the caller does, as p_sample does).
+ * noise: [N, per_sample] (rows of last / inactive images are not read).  N <= 65535. */
+int bbdm_bb_p_sample_step_batched_f32(const float* x_t, const float* y, const float* pred, const float* noise,
+                                      const float* m_t, const float* variance_t, const int64_t* t, const int64_t* t_next,
+                                      const int64_t* flag, float eta, int clip, int objective, float* x_next,
+                                      float* x0_recon, float* x_next_alias, int N, int per_sample, void* stream);
 /* predict_x0_from_objective alone (BBM.py:148-160), per-sample t (used by p_losses :121). */
 int bbdm_bb_predict_x0_f32(const float* x_t, const float* y, const float* pred, const int64_t* t,
                            const float* m_t, const float* variance_t, float* x0_recon,
