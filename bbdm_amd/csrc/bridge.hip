@@ -5,6 +5,7 @@
 // directly), th.cat([x, context], 1) (openaimodel.py:742) and the NCHW<->NHWC hand-over at the UNet boundary.
 // Compiled with -ffp-contract=off: the reference evaluates these formulas as separate fp32 tensor ops.
 #include "common.h"
+#include "philox.h"
 #include "stats_acc.h"
 
 namespace {
@@ -130,6 +131,157 @@ __global__ void p_step_batched_kernel(const float* __restrict__ x_t, const float
     }
 }
 
+// ---- seed-addressed noise (philox.h): the normals are a function of (seed, ordinal, domain, element) and never touch memory in the
+// fused kernels.  One image per blockIdx.y; a thread owns groups of four consecutive elements of it (one Philox call per group:
+// its four words are the group's four normals).  VEC: per_sample % 4 == 0 and 16-byte aligned pointers (the launchers check), one
+// 128-bit access per tensor and group; otherwise element accesses with the image's tail (per_sample % 4 elements) guarded.
+template <bool VEC>
+__device__ __forceinline__ void load_group(const float* __restrict__ p, int count, float v[4]) {
+    if (VEC) {
+        const float4 f = *reinterpret_cast<const float4*>(p);
+        v[0] = f.x, v[1] = f.y, v[2] = f.z, v[3] = f.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < count ? p[j] : 0.f;
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store_group(float* __restrict__ p, int count, const float v[4]) {
+    if (VEC) {
+        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < count) p[j] = v[j];
+    }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) philox_normal_kernel(float* __restrict__ out, const int64_t* __restrict__ seed_arr,
+                                                            const int64_t* __restrict__ ordinal_arr, unsigned domain,
+                                                            int per_sample) {
+    const int n = blockIdx.y;
+    const int64_t seed = seed_arr[n], ordinal = ordinal_arr[n];
+    float* o = out + (size_t)n * per_sample;
+    const unsigned groups = ((unsigned)per_sample + 3u) / 4u;
+    for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < groups; q += gridDim.x * 256u) {
+        float z[4];
+        philox_normal4(seed, ordinal, domain, q, z);
+        store_group<VEC>(o + 4 * (size_t)q, per_sample - (int)(4u * q), z);
+    }
+}
+
+// Debug / test entry: the raw Philox4x32-10 words of n (counter, key) pairs through the device build of philox.h.
+__global__ void philox_raw_kernel(const uint32_t* __restrict__ ck, uint32_t* __restrict__ out, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        uint32_t r[4];
+        philox4x32_10(ck[6 * i], ck[6 * i + 1], ck[6 * i + 2], ck[6 * i + 3], ck[6 * i + 4], ck[6 * i + 5], r);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[4 * i + j] = r[j];
+    }
+}
+
+// p_step_batched_kernel with the noise generated in registers (domain 0): the same (t, t_next, flag) per image and the same float
+// expressions in the same order, so it equals p_step_batched_kernel fed philox_normal_kernel's tensor bit for bit.  Last-step and
+// inactive images generate nothing.
+template <bool VEC>
+__global__ void __launch_bounds__(256) p_step_philox_kernel(const float* __restrict__ x_t, const float* __restrict__ y,
+                                                            const float* __restrict__ pred, const int64_t* __restrict__ seed_arr,
+                                                            const int64_t* __restrict__ ordinal_arr,
+                                                            const float* __restrict__ m_tab, const float* __restrict__ var_tab,
+                                                            const int64_t* __restrict__ t_arr,
+                                                            const int64_t* __restrict__ t_next_arr,
+                                                            const int64_t* __restrict__ flag_arr, float eta, int clip,
+                                                            int objective, float* __restrict__ x_next,
+                                                            float* __restrict__ x0_recon, float* __restrict__ x_next_alias,
+                                                            int per_sample) {
+    const int n = blockIdx.y;
+    const int64_t flag = flag_arr[n];
+    if (flag == 2) return;
+    const int is_last = flag == 1;
+    const int64_t t = t_arr[n];
+    const float m_t = m_tab[t], var_t = var_tab[t];
+    const float sig_obj = sqrtf(var_t);
+    float m_nt = 0.f, sigma_t = 0.f, coef = 0.f;
+    int64_t seed = 0, ordinal = 0;
+    if (!is_last) {
+        const int64_t t_next = t_next_arr[n];
+        m_nt = m_tab[t_next];
+        const float var_nt = var_tab[t_next];
+        const float a = (1.f - m_t) * (1.f - m_t);
+        const float b = (1.f - m_nt) * (1.f - m_nt);
+        const float sigma2 = (var_t - var_nt * a / b) * var_nt / var_t;
+        sigma_t = sqrtf(sigma2) * eta;
+        coef = sqrtf((var_nt - sigma2) / var_t);
+        seed = seed_arr[n];
+        ordinal = ordinal_arr[n];
+    }
+    const size_t base = (size_t)n * per_sample;
+    const unsigned groups = ((unsigned)per_sample + 3u) / 4u;
+    for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < groups; q += gridDim.x * 256u) {
+        const size_t i = base + 4 * (size_t)q;
+        const int count = per_sample - (int)(4u * q);          // >= 4 except in the image's last group
+        float xt[4], yy[4], pr[4], z[4] = {0.f, 0.f, 0.f, 0.f}, x0v[4], xnv[4];
+        load_group<VEC>(x_t + i, count, xt);
+        load_group<VEC>(y + i, count, yy);
+        load_group<VEC>(pred + i, count, pr);
+        if (!is_last) philox_normal4(seed, ordinal, BBDM_NOISE_P_SAMPLE, q, z);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float x0r = predict_x0_one(objective, xt[j], yy[j], pr[j], m_t, sig_obj);
+            if (clip) x0r = fminf(fmaxf(x0r, -1.f), 1.f);
+            x0v[j] = x0r;
+            if (is_last) {
+                xnv[j] = x0r;
+            } else {
+                const float mean = (1.f - m_nt) * x0r + m_nt * yy[j] + coef * (xt[j] - (1.f - m_t) * x0r - m_t * yy[j]);
+                xnv[j] = mean + sigma_t * z[j];
+            }
+        }
+        store_group<VEC>(x0_recon + i, count, x0v);
+        store_group<VEC>(x_next + i, count, xnv);
+        if (x_next_alias) store_group<VEC>(x_next_alias + i, count, xnv);
+    }
+}
+
+// q_sample_kernel with the noise generated in registers (domain 1), one image per blockIdx.y.
+template <bool VEC>
+__global__ void __launch_bounds__(256) q_sample_philox_kernel(const float* __restrict__ x0, const float* __restrict__ y,
+                                                              const int64_t* __restrict__ seed_arr,
+                                                              const int64_t* __restrict__ ordinal_arr,
+                                                              const int64_t* __restrict__ t, const float* __restrict__ m_t,
+                                                              const float* __restrict__ var_t, float* __restrict__ x_t,
+                                                              float* __restrict__ target, int per_sample, int objective) {
+    const int n = blockIdx.y;
+    const int64_t tt = t[n];
+    const float m = m_t[tt];
+    const float sig = sqrtf(var_t[tt]);
+    const int64_t seed = seed_arr[n], ordinal = ordinal_arr[n];
+    const size_t base = (size_t)n * per_sample;
+    const unsigned groups = ((unsigned)per_sample + 3u) / 4u;
+    for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < groups; q += gridDim.x * 256u) {
+        const size_t i = base + 4 * (size_t)q;
+        const int count = per_sample - (int)(4u * q);
+        float av[4], bv[4], z[4], xv[4], tv[4];
+        load_group<VEC>(x0 + i, count, av);
+        load_group<VEC>(y + i, count, bv);
+        philox_normal4(seed, ordinal, BBDM_NOISE_Q_SAMPLE, q, z);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a = av[j], b = bv[j], e = z[j];
+            float tg;
+            if (objective == 0) tg = m * (b - a) + sig * e;
+            else if (objective == 1) tg = e;
+            else tg = b - a;
+            xv[j] = (1.f - m) * a + m * b + sig * e;
+            tv[j] = tg;
+        }
+        store_group<VEC>(x_t + i, count, xv);
+        store_group<VEC>(target + i, count, tv);
+    }
+}
+
 __global__ void __launch_bounds__(256) loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            unsigned long long* __restrict__ partial, size_t count, int loss_type) {
     __shared__ double red[4];
@@ -191,6 +343,14 @@ inline unsigned ew_blocks(size_t total) {
     return (unsigned)(b > 8192 ? 8192 : (b ? b : 1));
 }
 
+// grid of the one-image-per-blockIdx.y kernels above: groups of four elements, 256 per block
+inline dim3 group_grid(int N, int per_sample) {
+    const size_t b = ((size_t)per_sample + 1023) / 1024;
+    return dim3((unsigned)(b > 2048 ? 2048 : b), (unsigned)N);
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
 }  // namespace
 
 extern "C" int bbdm_bb_q_sample_f32(const float* x0, const float* y, const float* noise, const int64_t* t,
@@ -245,6 +405,70 @@ extern "C" int bbdm_bb_p_sample_step_batched_f32(const float* x_t, const float* 
     hipLaunchKernelGGL(p_step_batched_kernel, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x_t, y, pred, noise,
                        m_t, variance_t, t, t_next, flag, eta, clip, objective, x_next, x0_recon, x_next_alias, per_sample);
     BBDM_CHECK_LAUNCH("p_sample_step_batched");
+    return BBDM_OK;
+}
+
+extern "C" int bbdm_philox_normal_f32(float* out, const int64_t* seed, const int64_t* ordinal, int domain, int N,
+                                      int per_sample, void* stream) {
+    BBDM_REQUIRE(out && seed && ordinal, "philox_normal: null pointer");
+    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && domain >= 0, "philox_normal: bad args");
+    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32), "philox_normal: per_sample / 4 must fit the 32-bit counter word");
+    const dim3 grid = group_grid(N, per_sample);
+    if (per_sample % 4 == 0 && aligned16(out))
+        hipLaunchKernelGGL(philox_normal_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, out, seed, ordinal,
+                           (unsigned)domain, per_sample);
+    else
+        hipLaunchKernelGGL(philox_normal_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, seed, ordinal,
+                           (unsigned)domain, per_sample);
+    BBDM_CHECK_LAUNCH("philox_normal");
+    return BBDM_OK;
+}
+
+extern "C" int bbdm_philox_raw_u32(const uint32_t* counter_key, uint32_t* out, int n, void* stream) {
+    BBDM_REQUIRE(counter_key && out && n > 0, "philox_raw: bad args");
+    hipLaunchKernelGGL(philox_raw_kernel, dim3(ew_blocks((size_t)n)), dim3(256), 0, (hipStream_t)stream, counter_key, out, n);
+    BBDM_CHECK_LAUNCH("philox_raw");
+    return BBDM_OK;
+}
+
+extern "C" int bbdm_bb_p_sample_step_philox_f32(const float* x_t, const float* y, const float* pred, const int64_t* seed,
+                                                const int64_t* ordinal, const float* m_t, const float* variance_t,
+                                                const int64_t* t, const int64_t* t_next, const int64_t* flag, float eta,
+                                                int clip, int objective, float* x_next, float* x0_recon, float* x_next_alias,
+                                                int N, int per_sample, void* stream) {
+    BBDM_REQUIRE(x_t && y && pred && seed && ordinal && m_t && variance_t && t && t_next && flag && x_next && x0_recon,
+                 "p_sample_step_philox: null pointer");
+    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "p_sample_step_philox: bad args");
+    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32),
+                 "p_sample_step_philox: per_sample / 4 must fit the 32-bit counter word");
+    const dim3 grid = group_grid(N, per_sample);
+    const bool vec = per_sample % 4 == 0 && aligned16(x_t) && aligned16(y) && aligned16(pred) && aligned16(x_next) &&
+                     aligned16(x0_recon) && aligned16(x_next_alias);
+    if (vec)
+        hipLaunchKernelGGL(p_step_philox_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal, m_t,
+                           variance_t, t, t_next, flag, eta, clip, objective, x_next, x0_recon, x_next_alias, per_sample);
+    else
+        hipLaunchKernelGGL(p_step_philox_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal, m_t,
+                           variance_t, t, t_next, flag, eta, clip, objective, x_next, x0_recon, x_next_alias, per_sample);
+    BBDM_CHECK_LAUNCH("p_sample_step_philox");
+    return BBDM_OK;
+}
+
+extern "C" int bbdm_bb_q_sample_philox_f32(const float* x0, const float* y, const int64_t* seed, const int64_t* ordinal,
+                                           const int64_t* t, const float* m_t, const float* variance_t, float* x_t,
+                                           float* target, int N, int per_sample, int objective, void* stream) {
+    BBDM_REQUIRE(x0 && y && seed && ordinal && t && m_t && variance_t && x_t && target, "q_sample_philox: null pointer");
+    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "q_sample_philox: bad args");
+    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32),
+                 "q_sample_philox: per_sample / 4 must fit the 32-bit counter word");
+    const dim3 grid = group_grid(N, per_sample);
+    if (per_sample % 4 == 0 && aligned16(x0) && aligned16(y) && aligned16(x_t) && aligned16(target))
+        hipLaunchKernelGGL(q_sample_philox_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x0, y, seed, ordinal, t, m_t,
+                           variance_t, x_t, target, per_sample, objective);
+    else
+        hipLaunchKernelGGL(q_sample_philox_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x0, y, seed, ordinal, t, m_t,
+                           variance_t, x_t, target, per_sample, objective);
+    BBDM_CHECK_LAUNCH("q_sample_philox");
     return BBDM_OK;
 }
 

@@ -8,12 +8,15 @@ the same names, argument meaning and error behaviour (asserts / NotImplementedEr
 
 What changed underneath: ``denoise_fn`` is :class:`bbdm_amd.unet.UNetModel` (HIP kernels), and the scheduler
 arithmetic (q_sample / predict_x0 / the p_sample update / the loss) are fused HIP kernels reached through the
-C-ABI of ``include/bbdm_hip.h``.  Random numbers still come from torch's generator (``torch.randn_like`` /
-``torch.randint``), so ``main.py``'s seeding (main.py:57-65) keeps its meaning.  No CPU fallback exists.
+C-ABI of ``include/bbdm_hip.h``.  Random numbers come from torch's generator by default (``torch.randn_like`` /
+``torch.randint``), so ``main.py``'s seeding (main.py:57-65) keeps its meaning.  With ``seeds=`` the noise is generated on the
+device inside the fused kernels instead, as a function of (seed, ordinal, element) -- :func:`philox_normal`, DESIGN.md
+"Seed-addressed noise".  No CPU fallback exists.
 """
 from __future__ import annotations
 
 import itertools
+import numbers
 import numpy as np
 import torch
 import torch.nn as nn
@@ -43,6 +46,51 @@ def _launch(t: torch.Tensor, name: str, *args):
 
 def _f32c(t):
     return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
+
+
+NOISE_P_SAMPLE, NOISE_Q_SAMPLE = 0, 1          # the `domain` word of the noise counter (csrc/philox.h)
+
+
+def _as_int64(v: int) -> int:
+    """A Python integer as the int64 with the same low 64 bits (seeds are 64-bit keys: 2**63 .. 2**64 - 1 wrap)."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _i64_per_image(v, n, device, what):
+    """``v`` (int64 tensor, sequence of ints or one int for all) as a contiguous int64 tensor [n] on ``device``."""
+    if isinstance(v, torch.Tensor):
+        if v.dtype != torch.int64:
+            raise TypeError(f"{what} must be an int64 tensor or a sequence of ints, got a {v.dtype} tensor")
+        out = v.reshape(-1).to(device).contiguous()
+    else:
+        vals = [v] * n if isinstance(v, numbers.Integral) else list(v)
+        out = torch.tensor([_as_int64(x) for x in vals], dtype=torch.int64).to(device)
+    if out.numel() != n:
+        raise ValueError(f"{what}: {out.numel()} values for {n} images")
+    return out
+
+
+def philox_normal(shape_per_image, seeds, ordinals, domain=NOISE_P_SAMPLE, device=None):
+    """Seed-addressed standard normals ``[N, *shape_per_image]`` (fp32): image n is a function of ``(seeds[n], ordinals[n],
+    domain)`` alone -- Philox4x32-10 keyed by the seed, counter = (element / 4, ordinal, domain), Box-Muller on the four output
+    words (csrc/philox.h; the layout is a compatibility contract).  These are the bits the fused kernels consume when
+    ``p_sample`` / ``BridgeSampler`` / ``q_sample`` are given seeds: ``domain`` 0 is the noise of ``p_sample`` at
+    ``ordinal = i`` (the position in ``model.steps``), 1 the noise of ``q_sample``.  ``seeds``: int64 tensor or sequence of ints
+    (its length is N); ``ordinals``: the same, or one int for all images.  ``device``: defaults to the seeds' device when they
+    are a tensor, else the current GPU."""
+    shape = tuple(int(d) for d in shape_per_image)
+    if device is None:
+        device = seeds.device if isinstance(seeds, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    n = seeds.numel() if isinstance(seeds, torch.Tensor) else len(seeds)
+    sd = _i64_per_image(seeds, n, device, "seeds")
+    od = _i64_per_image(ordinals, n, device, "ordinals")
+    out = torch.empty((n,) + shape, dtype=torch.float32, device=device)
+    _need_gpu(out)
+    if n and out[0].numel():
+        _launch(out, "bbdm_philox_normal_f32", out.data_ptr(), sd.data_ptr(), od.data_ptr(), int(domain), n, out[0].numel())
+    return out
 
 
 def bridge_schedule(T, mt_type, max_var, skip_sample, sample_type, sample_step):
@@ -144,12 +192,15 @@ class BrownianBridgeModel(nn.Module):
         t = torch.randint(0, self.num_timesteps, (b,), device=device).long()
         return self.p_losses(x, y, context, t)
 
-    def p_losses(self, x0, y, context, t, noise=None):
-        """BrownianBridgeModel.py:98-126."""
+    def p_losses(self, x0, y, context, t, noise=None, seeds=None, ordinals=None):
+        """BrownianBridgeModel.py:98-126.  ``seeds`` (one per sample, e.g. base + dataset index; ``ordinals`` default 0, meant for
+        the caller's global step): the noise is generated inside the q_sample kernel, a function of (seed, ordinal) that does not
+        depend on how the samples are sharded over ranks."""
         if self.loss_type not in _LOSSES:
             raise NotImplementedError()
-        noise = torch.randn_like(x0) if noise is None else noise
-        x_t, objective = self.q_sample(x0, y, t, noise)
+        if seeds is None:
+            noise = torch.randn_like(x0) if noise is None else noise
+        x_t, objective = self.q_sample(x0, y, t, noise, seeds=seeds, ordinals=ordinals)
         objective_recon = self.denoise_fn(x_t, timesteps=t, context=context)
         if objective_recon.requires_grad:
             from .autograd import bb_loss      # differentiable HIP loss (training path)
@@ -169,10 +220,17 @@ class BrownianBridgeModel(nn.Module):
                   _LOSSES[self.loss_type])
         return out[0]
 
-    def q_sample(self, x0, y, t, noise=None):
-        """BrownianBridgeModel.py:128-146 -> (x_t, objective)."""
+    def q_sample(self, x0, y, t, noise=None, seeds=None, ordinals=None):
+        """BrownianBridgeModel.py:128-146 -> (x_t, objective).  With ``seeds``: noise = philox_normal(shape, seeds, ordinals,
+        domain=1), generated in the kernel's registers."""
         if self.objective not in _OBJECTIVES:
             raise NotImplementedError()
+        if seeds is not None:
+            if noise is not None:
+                raise ValueError("q_sample: pass noise or seeds, not both")
+            return self._q_sample_seeded(x0, y, t, seeds, 0 if ordinals is None else ordinals)
+        if ordinals is not None:
+            raise ValueError("q_sample: ordinals without seeds")
         noise = torch.randn_like(x0) if noise is None else noise
         _need_gpu(x0, y, noise, t)
         x0c, yc, nc = _f32c(x0), _f32c(y), _f32c(noise)
@@ -181,6 +239,19 @@ class BrownianBridgeModel(nn.Module):
         _launch(x0c, "bbdm_bb_q_sample_f32", x0c.data_ptr(), yc.data_ptr(), nc.data_ptr(), tc.data_ptr(),
                   self.m_t.data_ptr(), self.variance_t.data_ptr(), x_t.data_ptr(), target.data_ptr(),
                   x0c.shape[0], x0c[0].numel(), _OBJECTIVES[self.objective])
+        return x_t, target
+
+    def _q_sample_seeded(self, x0, y, t, seeds, ordinals):
+        _need_gpu(x0, y, t)
+        x0c, yc = _f32c(x0), _f32c(y)
+        tc = t.to(torch.int64).contiguous()
+        n = x0c.shape[0]
+        sd = _i64_per_image(seeds, n, x0c.device, "seeds")
+        od = _i64_per_image(ordinals, n, x0c.device, "ordinals")
+        x_t, target = torch.empty_like(x0c), torch.empty_like(x0c)
+        _launch(x0c, "bbdm_bb_q_sample_philox_f32", x0c.data_ptr(), yc.data_ptr(), sd.data_ptr(), od.data_ptr(), tc.data_ptr(),
+                  self.m_t.data_ptr(), self.variance_t.data_ptr(), x_t.data_ptr(), target.data_ptr(), n, x0c[0].numel(),
+                  _OBJECTIVES[self.objective])
         return x_t, target
 
     def predict_x0_from_objective(self, x_t, y, t, objective_recon):
@@ -208,8 +279,9 @@ class BrownianBridgeModel(nn.Module):
 
     # ------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def p_sample(self, x_t, y, context, i, clip_denoised=False):
-        """BrownianBridgeModel.py:171-201: one UNet call + ONE fused update kernel -> (x_{t-1}, x0_recon)."""
+    def p_sample(self, x_t, y, context, i, clip_denoised=False, seeds=None):
+        """BrownianBridgeModel.py:171-201: one UNet call + ONE fused update kernel -> (x_{t-1}, x0_recon).  ``seeds`` (one per
+        image): the step's noise is philox_normal(shape, seeds, i), generated inside the update kernel."""
         if self.objective not in _OBJECTIVES:
             raise NotImplementedError
         _need_gpu(x_t, y)
@@ -231,10 +303,25 @@ class BrownianBridgeModel(nn.Module):
             t = torch.full((x_t.shape[0],), step, device=x_t.device, dtype=torch.long)
             objective_recon = fn(x_t, timesteps=t, context=context)
         is_last = step == 0
-        noise = None if is_last else torch.randn_like(x_t)
         x_next, x0_recon = torch.empty_like(x_t), torch.empty_like(x_t)
         # the loop feeds x_next back as the next x_t (BrownianBridgeModel.py:218-220): the step writes it into the plan's input buffer too
         alias = None if (plan is None or is_last) else plan.x_in
+        if seeds is not None:
+            n = x_t.shape[0]
+            sd = _i64_per_image(seeds, n, x_t.device, "seeds")
+            # step, next step, flag (0 a step with noise, 1 the last one) and ordinal of every image: one upload
+            idx = torch.tensor([[step] * n, [nxt] * n, [1 if is_last else 0] * n, [i] * n], dtype=torch.int64).to(x_t.device)
+            _launch(x_t, "bbdm_bb_p_sample_step_philox_f32", x_t.data_ptr(), y.data_ptr(), objective_recon.data_ptr(),
+                      sd.data_ptr(), idx[3].data_ptr(), self.m_t.data_ptr(), self.variance_t.data_ptr(), idx[0].data_ptr(),
+                      idx[1].data_ptr(), idx[2].data_ptr(), float(self.eta), 1 if clip_denoised else 0,
+                      _OBJECTIVES[self.objective], x_next.data_ptr(), x0_recon.data_ptr(),
+                      None if alias is None else alias.data_ptr(), n, x_t[0].numel())
+            if alias is not None:
+                plan.holds_input(x_next)
+            if is_last:
+                return x0_recon, x0_recon
+            return x_next, x0_recon
+        noise = None if is_last else torch.randn_like(x_t)
         _launch(x_t, "bbdm_bb_p_sample_step_f32", x_t.data_ptr(), y.data_ptr(), objective_recon.data_ptr(),
                   None if noise is None else noise.data_ptr(), self.m_t.data_ptr(), self.variance_t.data_ptr(),
                   step, 0 if is_last else steps[i + 1], 1 if is_last else 0, float(self.eta),
@@ -247,30 +334,33 @@ class BrownianBridgeModel(nn.Module):
         return x_next, x0_recon
 
     @torch.no_grad()
-    def p_sample_loop(self, y, context=None, clip_denoised=True, sample_mid_step=False):
-        """BrownianBridgeModel.py:203-221."""
+    def p_sample_loop(self, y, context=None, clip_denoised=True, sample_mid_step=False, seeds=None):
+        """BrownianBridgeModel.py:203-221.  ``seeds`` (int64 tensor or sequence, one per image): seed-addressed noise, step i of
+        image n drawing philox_normal(shape, seeds[n], i)."""
         if self.condition_key == "nocond":
             context = None
         else:
             context = y if context is None else context
+        if seeds is not None:
+            seeds = _i64_per_image(seeds, y.shape[0], y.device, "seeds")         # uploaded once for the whole loop
 
         if sample_mid_step:
             imgs, one_step_imgs = [y], []
             for i in tqdm(range(len(self.steps)), desc=f'sampling loop time step', total=len(self.steps)):
-                img, x0_recon = self.p_sample(x_t=imgs[-1], y=y, context=context, i=i, clip_denoised=clip_denoised)
+                img, x0_recon = self.p_sample(x_t=imgs[-1], y=y, context=context, i=i, clip_denoised=clip_denoised, seeds=seeds)
                 imgs.append(img)
                 one_step_imgs.append(x0_recon)
             return imgs, one_step_imgs
         else:
             img = y
             for i in tqdm(range(len(self.steps)), desc=f'sampling loop time step', total=len(self.steps)):
-                img, _ = self.p_sample(x_t=img, y=y, context=context, i=i, clip_denoised=clip_denoised)
+                img, _ = self.p_sample(x_t=img, y=y, context=context, i=i, clip_denoised=clip_denoised, seeds=seeds)
             return img
 
     @torch.no_grad()
-    def sample(self, y, context=None, clip_denoised=True, sample_mid_step=False):
+    def sample(self, y, context=None, clip_denoised=True, sample_mid_step=False, seeds=None):
         """BrownianBridgeModel.py:223-225."""
-        return self.p_sample_loop(y, context, clip_denoised, sample_mid_step)
+        return self.p_sample_loop(y, context, clip_denoised, sample_mid_step, seeds=seeds)
 
 
 def disabled_train(self, mode=True):
@@ -377,9 +467,9 @@ class LatentBrownianBridgeModel(BrownianBridgeModel):
         return self.vqgan.decode(z_q)
 
     @torch.no_grad()
-    def sample(self, x_cond, clip_denoised=False, sample_mid_step=False):
+    def sample(self, x_cond, clip_denoised=False, sample_mid_step=False, seeds=None):
         result = self.p_sample_loop(y=self.encode(x_cond, cond=True), context=self.get_cond_stage_context(x_cond),
-                                    clip_denoised=clip_denoised, sample_mid_step=sample_mid_step)
+                                    clip_denoised=clip_denoised, sample_mid_step=sample_mid_step, seeds=seeds)
         if not sample_mid_step:
             return self.decode(result, cond=False)
 

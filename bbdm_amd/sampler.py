@@ -15,15 +15,23 @@ drawn in step order, and nothing else draws from that generator.  The noise a re
 its batch-mates and its arrival time.  Its result still depends on its batch-mates through the fp16-pair bounds that the UNet plan takes
 over the batch (within tolerance, not bitwise).  A group of requests submitted together and run in lockstep computes exactly what
 ``model.sample`` computes on the same conditions with the same noise.
+
+``noise="philox"`` replaces that protocol by a formula: a request carries an ``int`` seed instead of a generator, and the noise of its
+step at position i of ``model.steps`` is ``bbdm_amd.philox_normal(shape, [seed], [i])`` (csrc/philox.h; DESIGN.md "Seed-addressed
+noise") -- a function of (seed, i, element) that needs no generator object, can be recomputed for one step alone, and is what
+``model.sample(..., seeds=...)`` draws for the same seed.  It is generated inside the bridge launch
+(``bbdm_bb_p_sample_step_philox_f32``): a step issues no ``normal_`` launch and the sampler holds no noise buffer; seeds and positions
+travel in the index tensor that a step uploads anyway.
 """
 from __future__ import annotations
 
 import collections
+import numbers
 from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
-from .model import BrownianBridgeModel, LatentBrownianBridgeModel, _OBJECTIVES, _f32c, _launch
+from .model import BrownianBridgeModel, LatentBrownianBridgeModel, _OBJECTIVES, _as_int64, _f32c, _launch
 from .unet import UNetModel
 
 _STEP, _LAST, _IDLE = 0, 1, 2          # per-slot flags of bbdm_bb_p_sample_step_batched_f32
@@ -44,15 +52,16 @@ def _pow2(k: int) -> int:
 
 
 class BridgeSampler:
-    """``BridgeSampler(model, batch_size, clip_denoised=False)`` for a :class:`BrownianBridgeModel` or
-    :class:`LatentBrownianBridgeModel` in ``eval()``.
+    """``BridgeSampler(model, batch_size, clip_denoised=False, noise="torch")`` for a :class:`BrownianBridgeModel` or
+    :class:`LatentBrownianBridgeModel` in ``eval()``.  ``noise``: ``"torch"`` (a ``torch.Generator`` per request) or ``"philox"`` (an
+    ``int`` seed per request; see the module docstring).
 
-    ``submit([(key, x_cond, generator), ...])`` queues a group of requests (``x_cond``: one condition image ``[C, H, W]``); iterating
+    ``submit([(key, x_cond, generator_or_seed), ...])`` queues a group of requests (``x_cond``: one condition image ``[C, H, W]``); iterating
     over the sampler runs steps until every queued request has finished and yields ``(key, sample)`` as each one does -- in pixel space
     (LBBDM: ``decode(latent, cond=False)``).  ``sample_set`` is the ``sample_to_eval``-shaped helper.  All requests share
     ``model.steps`` and one sample shape."""
 
-    def __init__(self, model: BrownianBridgeModel, batch_size: int, clip_denoised: bool = False):
+    def __init__(self, model: BrownianBridgeModel, batch_size: int, clip_denoised: bool = False, noise: str = "torch"):
         if not isinstance(model, BrownianBridgeModel):
             raise TypeError("BridgeSampler drives a bbdm_amd BrownianBridgeModel / LatentBrownianBridgeModel")
         if not isinstance(model.denoise_fn, UNetModel):
@@ -61,6 +70,9 @@ class BridgeSampler:
             raise NotImplementedError
         if int(batch_size) < 1 or int(batch_size) > 65535:
             raise ValueError(f"batch_size must be in [1, 65535], got {batch_size}")
+        if noise not in ("torch", "philox"):
+            raise ValueError(f"noise must be 'torch' or 'philox', got {noise!r}")
+        self.philox = noise == "philox"
         self.model, self.width, self.clip = model, int(batch_size), bool(clip_denoised)
         self.latent = isinstance(model, LatentBrownianBridgeModel)
         self.device = model.m_t.device
@@ -102,6 +114,12 @@ class BridgeSampler:
         reqs = list(requests)
         if not reqs:
             return
+        for _, _, gen in reqs:
+            is_seed = isinstance(gen, numbers.Integral) and not isinstance(gen, bool)
+            if self.philox and not is_seed:
+                raise TypeError(f"noise='philox' takes an int seed per request, got {type(gen).__name__}")
+            if not self.philox and is_seed:
+                raise TypeError("noise='torch' takes a torch.Generator per request, got an int (seeds belong to noise='philox')")
         self._check_schedule()
         rows, uniq = [], {}
         for _, c, _ in reqs:          # requests that pass the same tensor object share its row (sample_set: sample_num draws per condition)
@@ -121,7 +139,7 @@ class BridgeSampler:
             raise RuntimeError(f"condition of shape {shape} in a sampler of shape {self._shape} (one sample shape per sampler)")
         for key, c, gen in reqs:
             r = uniq[id(c)]
-            self._queue.append(_Request(key, y[r], None if ctx is None else ctx[r], gen))
+            self._queue.append(_Request(key, y[r], None if ctx is None else ctx[r], _as_int64(gen) if self.philox else gen))
 
     def _allocate(self, shape):
         self._shape = shape
@@ -130,7 +148,7 @@ class BridgeSampler:
         self._y = torch.zeros((W,) + shape[0], **f32)
         self._x = torch.zeros((W,) + shape[0], **f32)
         self._x_other = torch.zeros((W,) + shape[0], **f32)
-        self._noise = torch.zeros((W,) + shape[0], **f32)
+        self._noise = None if self.philox else torch.zeros((W,) + shape[0], **f32)      # philox: the noise never touches memory
         self._x0 = torch.zeros((W,) + shape[0], **f32)
         self._ctx = None if shape[1] is None else torch.zeros((W,) + shape[1], **f32)
 
@@ -180,6 +198,8 @@ class BridgeSampler:
         steps = m._steps_host()
         n = len(steps)
         idx = [[0] * W, [0] * W, [_IDLE] * W]           # step, next step, flag per slot
+        if self.philox:
+            idx += [[0] * W, [0] * W]                   # ... and the slot's seed and ordinal (its position in model.steps)
         for j in live:
             i = self._slots[j][1]
             step = steps[i]
@@ -188,17 +208,25 @@ class BridgeSampler:
                 idx[2][j] = _LAST
             else:
                 idx[1][j], idx[2][j] = steps[i + 1], _STEP
+                if self.philox:
+                    idx[3][j], idx[4][j] = self._slots[j][0].gen, i
         idx_d = torch.tensor(idx, dtype=torch.int64).to(self.device)
         pred, plan = m.denoise_fn.infer_steps(self._x, idx_d[0], self._ctx)
         self._plan = plan
-        for j in live:
-            if idx[2][j] == _STEP:       # == torch.randn(shape, generator=gen, device=dev): randn is empty(...).normal_(0, 1, gen)
-                self._noise[j].normal_(generator=self._slots[j][0].gen)
         x, xn = self._x, self._x_other
-        _launch(x, "bbdm_bb_p_sample_step_batched_f32", x.data_ptr(), self._y.data_ptr(), pred.data_ptr(), self._noise.data_ptr(),
-                m.m_t.data_ptr(), m.variance_t.data_ptr(), idx_d[0].data_ptr(), idx_d[1].data_ptr(), idx_d[2].data_ptr(),
-                float(m.eta), 1 if self.clip else 0, _OBJECTIVES[m.objective], xn.data_ptr(), self._x0.data_ptr(),
-                plan.x_in.data_ptr(), W, x[0].numel())
+        if self.philox:                  # the noise is generated inside the launch: philox_normal(shape, seed, i) per slot
+            _launch(x, "bbdm_bb_p_sample_step_philox_f32", x.data_ptr(), self._y.data_ptr(), pred.data_ptr(), idx_d[3].data_ptr(),
+                    idx_d[4].data_ptr(), m.m_t.data_ptr(), m.variance_t.data_ptr(), idx_d[0].data_ptr(), idx_d[1].data_ptr(),
+                    idx_d[2].data_ptr(), float(m.eta), 1 if self.clip else 0, _OBJECTIVES[m.objective], xn.data_ptr(),
+                    self._x0.data_ptr(), plan.x_in.data_ptr(), W, x[0].numel())
+        else:
+            for j in live:
+                if idx[2][j] == _STEP:   # == torch.randn(shape, generator=gen, device=dev): randn is empty(...).normal_(0, 1, gen)
+                    self._noise[j].normal_(generator=self._slots[j][0].gen)
+            _launch(x, "bbdm_bb_p_sample_step_batched_f32", x.data_ptr(), self._y.data_ptr(), pred.data_ptr(),
+                    self._noise.data_ptr(), m.m_t.data_ptr(), m.variance_t.data_ptr(), idx_d[0].data_ptr(), idx_d[1].data_ptr(),
+                    idx_d[2].data_ptr(), float(m.eta), 1 if self.clip else 0, _OBJECTIVES[m.objective], xn.data_ptr(),
+                    self._x0.data_ptr(), plan.x_in.data_ptr(), W, x[0].numel())
         plan.holds_input(xn)                        # x_in holds x_next (the kernel's second destination): the next call copies nothing
         self._x, self._x_other = xn, x
         done = []
@@ -231,7 +259,8 @@ class BridgeSampler:
     def sample_set(self, conds: torch.Tensor, sample_num: int, seeds: Sequence[int], group: int = 8) -> torch.Tensor:
         """``sample_to_eval``'s sampling (BBDMRunner.py:224-253) over a whole test set: ``sample_num`` samples of each of the M
         conditions ``conds`` [M, C, H, W].  Each test batch of ``group`` conditions is submitted as one group; the sample (m, s) draws
-        its noise from a generator on the model's device seeded with ``seeds[m * sample_num + s]``.  Returns [M, sample_num, C, H, W]."""
+        its noise from a generator on the model's device seeded with ``seeds[m * sample_num + s]`` (``noise="philox"``: that seed is
+        the request's Philox key, passed straight through).  Returns [M, sample_num, C, H, W]."""
         M = conds.shape[0]
         seeds = [int(s) for s in torch.as_tensor(seeds).reshape(-1).tolist()]
         if len(seeds) != M * sample_num:
@@ -241,8 +270,10 @@ class BridgeSampler:
             for mi in range(b0, min(M, b0 + group)):
                 c = conds[mi]
                 for s in range(sample_num):
-                    g = torch.Generator(device=self.device)
-                    g.manual_seed(seeds[mi * sample_num + s])
+                    g = seeds[mi * sample_num + s]
+                    if not self.philox:
+                        g = torch.Generator(device=self.device)
+                        g.manual_seed(seeds[mi * sample_num + s])
                     reqs.append(((mi, s), c, g))
             self.submit(reqs)
         out = None

@@ -330,6 +330,34 @@ int bbdm_bb_p_sample_step_batched_f32(const float* x_t, const float* y, const fl
                                       const float* m_t, const float* variance_t, const int64_t* t, const int64_t* t_next,
                                       const int64_t* flag, float eta, int clip, int objective, float* x_next,
                                       float* x0_recon, float* x_next_alias, int N, int per_sample, void* stream);
+/* ---- seed-addressed noise (ABI 27; csrc/philox.h, DESIGN.md "Seed-addressed noise") -----------------------------------
+ * Standard normals as a function of (seed, ordinal, domain, element): Philox4x32-10 with key = seed[n] (lo32, hi32) and
+ * counter = (e / 4, ordinal[n] lo32, ordinal[n] hi32, domain), e the element's flat index inside image n; the four output
+ * words give elements 4q .. 4q+3 by Box-Muller (u = ((r >> 8) + 0.5f) * 2^-24 in fp32; words 0, 1 -> the cos / sin pair
+ * 4q, 4q+1; words 2, 3 -> 4q+2, 4q+3).  domain: 0 the noise of p_sample, 1 the noise of q_sample.  This layout is a
+ * compatibility contract.  seed / ordinal: int64[N] on the device.  N <= 65535.
+ * bbdm_philox_normal_f32 writes the noise as a tensor out[N, per_sample]: the specification in executable form, and the
+ * same bits the fused kernels below consume in registers (one inline function, -ffp-contract=off). */
+int bbdm_philox_normal_f32(float* out, const int64_t* seed, const int64_t* ordinal, int domain, int N, int per_sample,
+                           void* stream);
+/* Debug / test entry: the raw Philox4x32-10 output words of n (counter, key) pairs.  counter_key: uint32 [n][6] =
+ * c0 c1 c2 c3 k0 k1; out: uint32 [n][4].  (The known-answer vectors of the generator are checked through it.) */
+int bbdm_philox_raw_u32(const uint32_t* counter_key, uint32_t* out, int n, void* stream);
+/* bbdm_bb_p_sample_step_batched_f32 with `noise` replaced by the per-image (seed, ordinal) of domain 0: the noise lives in
+ * registers only.  Same (t, t_next, flag) per image, same float expressions in the same order: it equals the batched
+ * kernel fed bbdm_philox_normal_f32's tensor bit for bit.  Last-step and inactive images read neither seed nor ordinal
+ * and generate nothing.  128-bit accesses when per_sample % 4 == 0 and every tensor pointer is 16-byte aligned, element
+ * accesses otherwise. */
+int bbdm_bb_p_sample_step_philox_f32(const float* x_t, const float* y, const float* pred, const int64_t* seed,
+                                     const int64_t* ordinal, const float* m_t, const float* variance_t, const int64_t* t,
+                                     const int64_t* t_next, const int64_t* flag, float eta, int clip, int objective,
+                                     float* x_next, float* x0_recon, float* x_next_alias, int N, int per_sample,
+                                     void* stream);
+/* bbdm_bb_q_sample_f32 with `noise` replaced by the per-image (seed, ordinal) of domain 1; for objective 'noise' the
+ * target is the generated value. */
+int bbdm_bb_q_sample_philox_f32(const float* x0, const float* y, const int64_t* seed, const int64_t* ordinal,
+                                const int64_t* t, const float* m_t, const float* variance_t, float* x_t, float* target,
+                                int N, int per_sample, int objective, void* stream);
 /* predict_x0_from_objective alone (BBM.py:148-160), per-sample t (used by p_losses :121). */
 int bbdm_bb_predict_x0_f32(const float* x_t, const float* y, const float* pred, const int64_t* t,
                            const float* m_t, const float* variance_t, float* x0_recon,

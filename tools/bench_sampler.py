@@ -5,7 +5,9 @@ on the C3 configuration: LBBDM-f4 UNet (latent 3x64x64, 200 steps), the HIP firs
 
   --mode baseline : ``net.sample(x_cond)`` ``sample_num`` times per test batch of ``--group`` (8), the reference's loop.  With
                     ``--root`` naming another checkout (the parent commit) its ``bbdm_amd`` and ``bench.py`` are imported instead.
-  --mode sampler  : ``BridgeSampler(model, --width).sample_set(conds, sample_num, seeds)`` (bbdm_amd/sampler.py).
+  --mode sampler  : ``BridgeSampler(model, --width).sample_set(conds, sample_num, seeds)`` (bbdm_amd/sampler.py).  ``--noise philox``:
+                    the sampler's seed-addressed noise, generated inside the bridge launch (no ``normal_`` launches); ``torch`` (the
+                    default) also runs against a ``--root`` checkout that predates the option.
 
 One untimed pass (``--warmup``) builds the plans and graphs; then ``--reps`` timed passes over the whole set, each ended by a device
 synchronisation.  Prints one JSON line: images per second of every repetition."""
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--group", type=int, default=8)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--noise", choices=("torch", "philox"), default="torch")
     args = ap.parse_args()
     root = os.path.abspath(args.root)
     sys.path.insert(0, root)
@@ -57,7 +60,7 @@ def main():
                     outs.append(model.sample(x_cond))
             return outs
     else:
-        sampler = bbdm_amd.BridgeSampler(model, args.width)
+        sampler = bbdm_amd.BridgeSampler(model, args.width, **({"noise": "philox"} if args.noise == "philox" else {}))
         seeds = list(range(n_img))
 
         def one_pass():
@@ -74,7 +77,7 @@ def main():
             torch.cuda.synchronize(dev)
             times.append(time.perf_counter() - t0)
             del out
-    line = {"mode": args.mode, "width": args.width if args.mode == "sampler" else args.group, "package": bbdm_amd.__file__,
+    line = {"mode": args.mode, "noise": args.noise if args.mode == "sampler" else "torch", "width": args.width if args.mode == "sampler" else args.group, "package": bbdm_amd.__file__,
             "images": n_img, "steps": len(model.steps), "seconds": [round(t, 3) for t in times],
             "imgs_per_s": [round(n_img / t, 3) for t in times]}
     print(json.dumps(line), flush=True)
