@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBDM_HIP_LIB overrides the library path (A/B runs of kernel variants); the default is the in-tree build
 LIB_PATH = os.environ.get("BBDM_HIP_LIB") or os.path.join(_HERE, "libbbdm_hip.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _P = c_void_p
 # name -> (restype, argtypes); must list every symbol of include/bbdm_hip.h (tests/test_abi.py checks it)
@@ -173,6 +173,13 @@ SIGNATURES = {
     "bbdm_opt_chunk_elems": (c_int, []),
     "bbdm_adam_ema_step_f32": (c_int, [_P, c_int, c_int, c_double, c_double, c_double, c_double, c_double,
                                        ctypes.c_longlong, c_int, c_double, _P]),
+    # global gradient-norm clipping + non-finite guard (ABI 28; csrc/optim.hip)
+    "bbdm_grad_norm_cells_bytes": (c_size_t, []),
+    "bbdm_grad_sqnorm_f32": (c_int, [_P, c_int, _P, _P]),
+    "bbdm_grad_norm_finalize_f32": (c_int, [_P, c_double, _P, _P, _P]),
+    "bbdm_adam_ema_step_clip_f32": (c_int, [_P, c_int, c_int, c_double, c_double, c_double, c_double, c_double,
+                                            ctypes.c_longlong, c_int, c_double, _P, c_int, _P]),
+    "bbdm_grad_scale_f32": (c_int, [_P, c_int, _P, _P]),
     "bbdm_set_option": (c_int, [c_char_p, c_int]),              # header: "options" (tests / tools A-B runs)
     "bbdm_get_option": (c_int, [c_char_p, _P]),
 }

@@ -15,6 +15,13 @@ chunk pointers: ONE launch updates all 248 tensors.  When the EMA update is due 
 it into the optimizer's pass with ``optimizer.step(ema=ema, ema_with_decay=...)``; called separately
 (`ema.update(net)`, the unmodified runner) it is its own single pass.  No CPU / PyTorch fallback: parameters must be fp32
 GPU tensors.
+
+Beyond the reference (which never clips): ``FusedAdam(..., max_grad_norm=, skip_nonfinite=)`` -- global L2 gradient-norm
+clipping and a non-finite-gradient guard, computed on the device by two small launches over the same chunk tables and
+applied INSIDE the Adam pass (no scale pass over the gradients, no host read-back); :func:`grad_norm` and
+:func:`clip_grad_norm_` are the standalone forms (``torch.nn.utils.clip_grad_norm_``'s signature, norm type 2) for the
+optimizers torch provides.  The norm is summed in a fixed order and accumulated in exact integer limbs
+(``csrc/stats_acc.h``): the same gradient values give the same bits on every run and on every rank.
 """
 from __future__ import annotations
 
@@ -26,7 +33,9 @@ import torch.nn as nn
 
 from . import _lib
 
-__all__ = ["FusedAdam", "EMA", "get_optimizer"]
+__all__ = ["FusedAdam", "EMA", "get_optimizer", "grad_norm", "clip_grad_norm_"]
+
+_UNSET = object()
 
 
 class _ChunkTable:
@@ -65,38 +74,117 @@ def _check_param(p: torch.Tensor):
         raise TypeError("bbdm_amd.optim works on contiguous fp32 parameters (the reference trains in fp32)")
 
 
-def _launch(device, table, n, do_adam, group, step, ema_mode, ema_decay):
+def _launch(device, table, n, do_adam, group, step, ema_mode, ema_decay, clip=None, skip_nonfinite=False):
+    """``clip`` (the 4-float device buffer :class:`_NormBuffers` ``.out``): the clipped entry point; None: the plain one."""
+    args = (table.data_ptr(), n, int(do_adam), float(group["lr"]) if group else 0.0,
+            float(group["betas"][0]) if group else 0.0, float(group["betas"][1]) if group else 0.0,
+            float(group["eps"]) if group else 0.0, float(group["weight_decay"]) if group else 0.0,
+            int(step), int(ema_mode), float(ema_decay))
     with _lib.device_guard(device):
-        _lib.call("bbdm_adam_ema_step_f32", table.data_ptr(), n, int(do_adam), float(group["lr"]) if group else 0.0,
-                  float(group["betas"][0]) if group else 0.0, float(group["betas"][1]) if group else 0.0,
-                  float(group["eps"]) if group else 0.0, float(group["weight_decay"]) if group else 0.0,
-                  int(step), int(ema_mode), float(ema_decay), _lib.current_stream(device))
+        if clip is None:
+            _lib.call("bbdm_adam_ema_step_f32", *args, _lib.current_stream(device))
+        else:
+            _lib.call("bbdm_adam_ema_step_clip_f32", *args, clip.data_ptr(), int(bool(skip_nonfinite)),
+                      _lib.current_stream(device))
+
+
+class _NormBuffers:
+    """What the norm kernels write, owned here (the library never allocates): the limb cells of the squared norm (zeroed
+    before each use), ``out`` = [norm, coef, ok, 0] fp32, and the int64 counter of skipped steps."""
+
+    def __init__(self, device):
+        self.cells = torch.zeros(_lib.load().bbdm_grad_norm_cells_bytes() // 8, dtype=torch.int64, device=device)
+        self.out = torch.zeros(4, dtype=torch.float32, device=device)
+        self.skipped = torch.zeros((), dtype=torch.int64, device=device)
+
+    def run(self, device, tables, max_norm, count_skips):
+        """One global norm over the gradients of ``tables`` [(device table, chunks)]: norm pass(es), then the finalize.
+        ``max_norm`` None: coef = 1 (no clipping).  Nothing is read back."""
+        self.cells.zero_()
+        with _lib.device_guard(device):
+            st = _lib.current_stream(device)
+            for table, n in tables:
+                _lib.call("bbdm_grad_sqnorm_f32", table.data_ptr(), n, self.cells.data_ptr(), st)
+            _lib.call("bbdm_grad_norm_finalize_f32", self.cells.data_ptr(), float("inf") if max_norm is None else float(max_norm),
+                      self.out.data_ptr(), self.skipped.data_ptr() if count_skips else None, st)
+
+
+def _check_max_norm(max_norm):
+    if max_norm is not None and not float(max_norm) >= 0.0:
+        raise ValueError(f"max_grad_norm={max_norm}: must be >= 0 (or None: no clipping)")
 
 
 class FusedAdam(torch.optim.Optimizer):
     """``torch.optim.Adam(params, lr, betas, eps, weight_decay)`` (no amsgrad / maximize) with the whole ``step()`` as
     one launch.  State layout = torch's: ``state[p]['step']`` (a float32 scalar tensor on the CPU, as torch keeps it for
     non-capturable Adam), ``'exp_avg'``, ``'exp_avg_sq'`` -- an optimizer checkpoint written by either loads into the
-    other."""
+    other.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
+    ``max_grad_norm`` (None: off): ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` over ALL parameters of ALL groups that
+    have a gradient (one global L2 norm), folded into the step: a norm pass and a one-workgroup finalize in front of the Adam
+    launch, which multiplies each gradient by ``min(1, max_grad_norm / (norm + 1e-6))`` as it reads it (``p.grad`` itself is
+    NOT rescaled).  ``skip_nonfinite``: when the norm is not finite (an Inf / NaN gradient, or a 16 384-element chunk whose norm
+    exceeds 65 536: the accumulator's window, csrc/optim.hip) the parameters and both moments stay untouched; a fused ``ema=``
+    update still happens, as the runner's ``ema.update`` would; ``skipped_steps`` counts these steps on the device.  Nothing on
+    the host knows about a skip -- no read-back, no sync -- so the host-side ``state[p]['step']`` (and with it the bias
+    correction of later steps) ADVANCES on a skipped step too.  Without ``skip_nonfinite`` a non-finite norm gives a NaN
+    coefficient and NaN parameters (every parameter, where torch's Inf norm -> coef 0 spoils only the elements whose gradient was
+    non-finite).  Both options are attributes of the optimizer, not entries of ``param_groups`` / ``defaults``: ``state_dict()``
+    keeps torch's layout.  All parameters with a gradient must then live on one device (``ValueError`` otherwise).  With both
+    off, ``step()`` is what it was: one ``bbdm_adam_ema_step_f32`` launch.
+
+    ``grad_norm``: the pre-clip global norm of the last clipped / guarded step, a 0-dim fp32 device tensor (a view of the
+    optimizer's buffer: the next such step overwrites it; ``.clone()`` to keep it).  NaN where ``skip_nonfinite`` skipped."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, max_grad_norm=None,
+                 skip_nonfinite=False):
         if amsgrad:
             raise NotImplementedError("bbdm_amd.optim.FusedAdam: amsgrad is not implemented (the reference never sets it)")
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError(f"invalid Adam hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=False, differentiable=False, fused=None))
+        _check_max_norm(max_grad_norm)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
         self._tables: Dict[tuple, _ChunkTable] = {}
+        self._norm: Optional[_NormBuffers] = None
+
+    def _norm_buffers(self, device=None) -> _NormBuffers:
+        if self._norm is None or (device is not None and self._norm.out.device != device):
+            self._norm = _NormBuffers(device if device is not None else self.param_groups[0]["params"][0].device)
+        return self._norm
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """Pre-clip global gradient norm of the last clipped / guarded step (None before the first one)."""
+        return None if self._norm is None else self._norm.out[0]
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """Number of steps the non-finite guard skipped: a 0-dim int64 DEVICE tensor (reading it is the caller's sync)."""
+        return self._norm_buffers().skipped
 
     @torch.no_grad()
-    def step(self, closure=None, ema: Optional["EMA"] = None, ema_with_decay: bool = True):
+    def step(self, closure=None, ema: Optional["EMA"] = None, ema_with_decay: bool = True, max_grad_norm=_UNSET,
+             skip_nonfinite=_UNSET):
         """One Adam step for every parameter that has a gradient.  ``ema`` (optional): also apply that EMA's update for
         these parameters in the same pass (``EMA.update(net, with_decay=ema_with_decay)`` semantics, on the updated
-        weights)."""
+        weights).  ``max_grad_norm`` / ``skip_nonfinite``: override the optimizer's attributes for this call."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        max_norm = self.max_grad_norm if max_grad_norm is _UNSET else max_grad_norm
+        skip = self.skip_nonfinite if skip_nonfinite is _UNSET else bool(skip_nonfinite)
+        _check_max_norm(max_norm)
+        clipped = max_norm is not None or skip
+        if clipped:                                   # ONE norm over every group: before any state is touched
+            devices = {p.device for group in self.param_groups for p in group["params"] if p.grad is not None}
+            if len(devices) > 1:
+                raise ValueError("bbdm_amd.optim.FusedAdam: max_grad_norm / skip_nonfinite need every parameter that has a "
+                                 f"gradient on ONE device (the norm is global); got {sorted(map(str, devices))}")
+        launches = []                                 # (device, table, chunks, do_adam, group, step, ema mode, decay, rows)
         for gi, group in enumerate(self.param_groups):
             kinds: Dict[tuple, list] = {}        # (device, step count) -> rows; normally ONE kind = one launch
             no_grad_rows = []                    # parameters without a gradient: no Adam update (as torch) -- but EMA.update covers
@@ -127,10 +215,20 @@ class FusedAdam(torch.optim.Optimizer):
                 by_dev.setdefault(r[0].device, []).append(r)
             for device, rows in by_dev.items():
                 table, n = self._tables.setdefault((gi, device, "ema-only"), _ChunkTable()).get(rows, device)
-                _launch(device, table, n, False, None, 0, mode, ema.ema_decay)
+                launches.append((device, table, n, False, None, 0, mode, ema.ema_decay, rows))
             for (device, step_no), rows in kinds.items():
                 table, n = self._tables.setdefault((gi, device, len(kinds) > 1 and step_no), _ChunkTable()).get(rows, device)
-                _launch(device, table, n, True, group, step_no, mode, ema.ema_decay if ema is not None else 0.0)
+                launches.append((device, table, n, True, group, step_no, mode, ema.ema_decay if ema is not None else 0.0, rows))
+        clip = None
+        if clipped:                                   # norm pass over the tables the Adam launches are about to use, then the finalize
+            adam = [l for l in launches if l[3]]
+            device = adam[0][0] if adam else self.param_groups[0]["params"][0].device
+            norm = self._norm_buffers(device)
+            norm.run(device, [(l[1], l[2]) for l in adam], max_norm, skip)
+            clip = norm.out
+        for device, table, n, do_adam, group, step_no, mode, decay, rows in launches:
+            _launch(device, table, n, do_adam, group, step_no, mode, decay, clip if do_adam else None, skip)
+            if do_adam:
                 # the kernel rewrote the parameters behind autograd's back: bump their version counters, as an in-place torch op
                 # would -- the UNet keys its packed weight copies (and autograd its saved-tensor checks) on them.  Without this the
                 # next forward ran on the conv weights of BEFORE the step.
@@ -200,11 +298,67 @@ class EMA:
         self.backup = {}
 
 
+_norm_tables: Dict[torch.device, _ChunkTable] = {}        # grad_norm / clip_grad_norm_: one cached table per device
+
+
+def _global_grad_norm(parameters, max_norm, norm_type):
+    """-> ([norm, coef, ok, 0] device buffer, function that applies ``grad *= coef``)."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError(f"bbdm_amd.optim: only the L2 norm (norm_type=2) is implemented, got norm_type={norm_type}")
+    _check_max_norm(max_norm)
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]          # as torch: a parameter without a gradient is left out
+    if not grads:
+        return torch.zeros(4), lambda: None
+    device = grads[0].device
+    for g in grads:
+        if g.device != device:
+            raise ValueError(f"bbdm_amd.optim: the gradients must live on one device, got {device} and {g.device}")
+        _lib.require_gpu(g)
+        if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous():
+            raise TypeError("bbdm_amd.optim: the gradient norm works on dense contiguous fp32 gradients")
+    table, n = _norm_tables.setdefault(device, _ChunkTable()).get([(g, g, None, None, None) for g in grads], device)
+    norm = _NormBuffers(device)                   # fresh per call: the returned norm is the caller's to keep
+    norm.run(device, [(table, n)], max_norm, False)
+
+    def scale():
+        with _lib.device_guard(device):
+            _lib.call("bbdm_grad_scale_f32", table.data_ptr(), n, norm.out.data_ptr(), _lib.current_stream(device))
+        torch.autograd.graph.increment_version(grads)
+    return norm.out, scale
+
+
+@torch.no_grad()
+def grad_norm(parameters, norm_type: float = 2.0) -> torch.Tensor:
+    """Global L2 norm of the gradients of ``parameters`` (a tensor or an iterable), a 0-dim fp32 tensor on their device: what
+    ``torch.nn.utils.clip_grad_norm_`` returns, without the clipping, a host read-back or an order-dependent sum (NaN where the
+    sum leaves the accumulator's window or a gradient is not finite: csrc/optim.hip)."""
+    return _global_grad_norm(parameters, None, norm_type)[0][0]
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False,
+                    foreach: Optional[bool] = None) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` (norm type 2 only) in three launches: gradients *= min(1, max_norm / (norm + 1e-6)) in
+    place; returns the norm before clipping.  For ``RMSprop`` / ``SGD`` from :func:`get_optimizer` (``FusedAdam`` clips inside its
+    own pass: ``max_grad_norm=``).  ``error_if_nonfinite`` reads the norm back (the one host sync here); ``foreach`` is accepted
+    and ignored."""
+    out, scale = _global_grad_norm(parameters, max_norm, norm_type)
+    if error_if_nonfinite and not bool(torch.isfinite(out[0])):
+        raise RuntimeError("bbdm_amd.optim.clip_grad_norm_: the total norm of the gradients is non-finite, so it cannot be "
+                           "clipped (error_if_nonfinite=True)")
+    scale()
+    return out[0]
+
+
 def get_optimizer(optim_config, parameters):
-    """runners/utils.py:48-57 with Adam -> :class:`FusedAdam`."""
+    """runners/utils.py:48-57 with Adam -> :class:`FusedAdam`.  Two optional keys beyond the reference's yaml:
+    ``max_grad_norm`` and ``skip_nonfinite`` (absent = off, the reference's behaviour)."""
     if optim_config.optimizer == 'Adam':
         return FusedAdam(parameters, lr=optim_config.lr, weight_decay=optim_config.weight_decay,
-                         betas=(optim_config.beta1, 0.999))
+                         betas=(optim_config.beta1, 0.999), max_grad_norm=getattr(optim_config, "max_grad_norm", None),
+                         skip_nonfinite=getattr(optim_config, "skip_nonfinite", False))
     elif optim_config.optimizer == 'RMSProp':
         return torch.optim.RMSprop(parameters, lr=optim_config.lr, weight_decay=optim_config.weight_decay)
     elif optim_config.optimizer == 'SGD':

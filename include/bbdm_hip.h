@@ -664,6 +664,32 @@ int bbdm_adam_ema_step_f32(const BbdmOptChunk* table, int nchunks, int do_adam, 
                            double eps, double weight_decay, long long step, int ema_mode, double ema_decay,
                            void* stream);
 
+/* ---- global gradient-norm clipping + non-finite guard (ABI 28; no reference counterpart: the reference never clips) ------- */
+/* torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm type 2) as two small launches in front of the Adam pass, on the SAME
+ * chunk tables, with no host read-back; the scaling by the clip coefficient happens inside the Adam pass.
+ *   bbdm_grad_norm_cells_bytes   : size of the accumulator the CALLER owns and ZEROES before the first bbdm_grad_sqnorm_f32 of a norm;
+ *   bbdm_grad_sqnorm_f32         : adds sum(grad^2) of every chunk with a non-NULL grad into `cells` -- per chunk a fixed-order fp64
+ *                                  sum, added as exact integer limbs (csrc/stats_acc.h), so the total depends on the gradient values and
+ *                                  the chunk boundaries only, not on the launch, the order of the workgroups or of the table's rows.
+ *                                  May be called for several tables before one finalize (one global norm).  Window: a chunk's sum of
+ *                                  squares must be < 2^32 (chunk norm < 65536) and is kept to 2^-88; outside it, or non-finite, the
+ *                                  norm is NaN (where torch's would be Inf or a large finite number);
+ *   bbdm_grad_norm_finalize_f32  : one workgroup: out[0] = norm (fp32), out[1] = coef = min(1, max_norm / (norm + 1e-6)) in fp32 as
+ *                                  torch forms it (reciprocal, then product; NaN when the norm is; max_norm = +inf: no clipping), out[2] = ok (1.0f, or 0.0f
+ *                                  when the norm is not finite), out[3] = 0.  `skipped` (may be NULL): an int64 DEVICE counter,
+ *                                  incremented when ok == 0;
+ *   bbdm_adam_ema_step_clip_f32  : bbdm_adam_ema_step_f32 with g * coef (one fp32 rounding, as grads.mul_(coef)) in place of g; `clip` =
+ *                                  the finalize's `out`.  skip_nonfinite != 0 and ok == 0: p, exp_avg, exp_avg_sq stay untouched, the
+ *                                  EMA part (if any) still runs.  coef == 1: the bits of bbdm_adam_ema_step_f32;
+ *   bbdm_grad_scale_f32          : grad *= coef for every chunk with a non-NULL grad (the standalone clip_grad_norm_). */
+size_t bbdm_grad_norm_cells_bytes(void);
+int bbdm_grad_sqnorm_f32(const BbdmOptChunk* table, int nchunks, unsigned long long* cells, void* stream);
+int bbdm_grad_norm_finalize_f32(const unsigned long long* cells, double max_norm, float* out, long long* skipped, void* stream);
+int bbdm_adam_ema_step_clip_f32(const BbdmOptChunk* table, int nchunks, int do_adam, double lr, double beta1, double beta2,
+                                double eps, double weight_decay, long long step, int ema_mode, double ema_decay,
+                                const float* clip, int skip_nonfinite, void* stream);
+int bbdm_grad_scale_f32(const BbdmOptChunk* table, int nchunks, const float* clip, void* stream);
+
 /* ---- sample egress ------------------------------------------------------------------------ */
 /* fp32 NCHW [N,C,H,W] -> uint8 NHWC [N,H,W,C] with the arithmetic of save_single_image (runners/utils.py:67-74):
  * to_normal != 0: v = clamp(v * 0.5 + 0.5, 0, 1); then u8 = (uint8) clamp(v * 255 + 0.5, 0, 255) (truncation) -- each
