@@ -9,7 +9,7 @@
 // Why this is not a reduced-precision mode.  What limits an fp32 GEMM on the matrix core is not the 2^-24 of its operands but the
 // chain of roundings of its fp32 accumulator: one per MFMA, each half an ulp of the running sum.  bf16x3 performs 6 K / 16 of them per
 // output, the f32 MFMA (v_mfma_f32_32x32x2_f32) K / 2, this path 3 K / 16.  Measured against fp64 (tests/test_kernels_gpu.py::
-// test_gemm_h2p_accuracy, tools/gemm_error_probe.py -> profiles/r06_gemm_error.txt) the h2 product is MORE accurate than either from
+// test_gemm_h2p_accuracy, tools/gemm_error_probe.py -> profiles/r06_gemm_error_{h2,bf3}.txt) the h2 product is MORE accurate than either from
 // K = 128 up, and through the ten-point Winograd transforms -- which amplify exactly that accumulated error -- it lowers the step's
 // parity error.
 //

@@ -21,30 +21,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+# (all of them stay names of this module: bench.py and the tests reach wino_planes, _ver, ... as bbdm_amd.unet.<name>)
+from .packing import _NoVersion, _PackedConv, _PackedWinograd, _RowL1Gain, _ver, _zero_on, wino_planes
 
 __all__ = ["UNetModel"]
-
-
-class _NoVersion:
-    """Stands in for the version of a tensor that has no version counter: never equal to anything.  (A FRESH instance per read:
-    container comparisons short-cut on identity.)"""
-
-    def __eq__(self, other):
-        return False
-
-    __hash__ = object.__hash__
-
-
-def _ver(t: torch.Tensor):
-    """``t._version``, or a :class:`_NoVersion` for inference tensors (``torch.inference_mode()``: no version counter).  The version
-    only tracks writes made through torch ops on ``t`` or its views -- a raw-pointer kernel or a DLPack consumer does not bump it --
-    so every cache keyed on it must tolerate a miss: a key containing a ``_NoVersion`` never matches, i.e. the copy / re-pack runs."""
-    if t.is_inference():
-        return _NoVersion()
-    try:
-        return t._version
-    except RuntimeError:
-        return _NoVersion()
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -330,282 +310,6 @@ class _Pre(tuple):
 
 def _round4(c):
     return (c + 3) // 4 * 4
-
-
-def _zero_on(t: torch.Tensor, stream):
-    """``t.zero_()`` enqueued on the raw HIP stream ``stream`` -- the stream the packing launches that follow are given.  (The training
-    plans re-pack their data-gradient operands on the plan's SECOND stream: a plain ``zero_()`` would go to torch's current stream and
-    race with the maximum those launches accumulate into ``t``.)"""
-    if t.is_cuda and stream:
-        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=t.device)):
-            t.zero_()
-    else:
-        t.zero_()
-
-
-class _PackedConv:
-    """Packed copy of one conv weight, refreshed when the parameter storage or version changes
-    (EMA swaps ``param.data`` without bumping ``_version`` -- runners/base/EMA.py:31-43 -- so both are keyed)."""
-
-    def __init__(self, weight: nn.Parameter, bias: Optional[nn.Parameter], cin_pad: int):
-        self.weight, self.bias = weight, bias
-        self.cout, self.cin = weight.shape[0], weight.shape[1]
-        self.ks = weight.shape[2] if weight.dim() == 4 else 1      # Conv1d k=1: [O, I, 1] == [O, I, 1, 1] in memory
-        self.cin_pad = cin_pad
-        n = _lib.load().bbdm_conv_packed_floats(self.cout, cin_pad, self.ks)
-        self.packed = torch.empty(n, dtype=torch.float32, device=weight.device)
-        self.packed.cin_true = self.cin          # algorithmic (unpadded) input channels, for flop accounting
-        self.key = None
-
-    def refresh(self, stream):
-        w = self.weight
-        key = (w.data_ptr(), _ver(w))
-        if key != self.key:
-            if not w.is_contiguous() or w.dtype != torch.float32:
-                raise RuntimeError("bbdm_amd: conv weights must be contiguous fp32")
-            _lib.call("bbdm_conv_pack_weight_f32", w.data_ptr(), self.packed.data_ptr(), self.cout, self.cin,
-                      self.cin_pad, self.ks, stream)
-            self.key = key
-
-
-class _PackedConvBf3(_PackedConv):
-    """A 1x1 conv / Linear weight split into the three bf16 planes of csrc/gemm_bf3.hip (``packed``); the fp32 packing is
-    kept as the intermediate."""
-
-    def __init__(self, weight, bias, cin_pad):
-        super().__init__(weight, bias, cin_pad)
-        self.packed_f32 = self.packed
-        nh = _lib.load().bbdm_gemm_bf3_packed_halfs(1, cin_pad, self.cout)
-        self.packed = torch.empty(nh, dtype=torch.int16, device=weight.device)
-        self.packed.cin_true = self.cin
-
-    def refresh(self, stream):
-        w = self.weight
-        key = (w.data_ptr(), _ver(w))
-        if key != self.key:
-            if not w.is_contiguous() or w.dtype != torch.float32:
-                raise RuntimeError("bbdm_amd: conv weights must be contiguous fp32")
-            _lib.call("bbdm_conv_pack_weight_f32", w.data_ptr(), self.packed_f32.data_ptr(), self.cout, self.cin,
-                      self.cin_pad, 1, stream)
-            _lib.call("bbdm_gemm_bf3_pack_f32", self.packed_f32.data_ptr(), self.packed.data_ptr(), 1, self.cin_pad, self.cout,
-                      stream)
-            self.key = key
-
-
-class _PackedConvBf3q(_PackedConv):
-    """A 1x1 conv / Linear weight as the B planes of csrc/gemm_bf3p.hip (``packed``; fragment-unit layout): the operand of
-    bbdm_conv1x1_bf3q_f32, the pipelined kernel that reads the fp32 activation as it lies in HBM."""
-
-    def __init__(self, weight, bias, cin_pad):
-        super().__init__(weight, bias, cin_pad)
-        self.packed_f32 = self.packed
-        self.packed = torch.empty(_lib.load().bbdm_gemm_bf3p_b_bytes(1, cin_pad, self.cout), dtype=torch.uint8, device=weight.device)
-        self.packed.cin_true = self.cin
-
-    def refresh(self, stream):
-        w = self.weight
-        key = (w.data_ptr(), _ver(w))
-        if key != self.key:
-            if not w.is_contiguous() or w.dtype != torch.float32:
-                raise RuntimeError("bbdm_amd: conv weights must be contiguous fp32")
-            _lib.call("bbdm_conv_pack_weight_f32", w.data_ptr(), self.packed_f32.data_ptr(), self.cout, self.cin,
-                      self.cin_pad, 1, stream)
-            _lib.call("bbdm_gemm_bf3p_pack_b_f32", self.packed_f32.data_ptr(), self.packed.data_ptr(), 1, self.cin_pad, self.cout,
-                      stream)
-            self.key = key
-
-
-class _PackedConvH2q(_PackedConv):
-    """A 1x1 conv / Linear weight as the fp16-pair B planes of csrc/gemm_bf3p.hip under the scale of its exact maximum (``ubound``): the
-    operand of bbdm_conv1x1_h2q_f32."""
-
-    def __init__(self, weight, bias, cin_pad):
-        super().__init__(weight, bias, cin_pad)
-        self.packed_f32 = self.packed
-        self.packed = torch.empty(_lib.load().bbdm_gemm_h2p_b_bytes(1, cin_pad, self.cout), dtype=torch.uint8, device=weight.device)
-        self.packed.cin_true = self.cin
-        self.ubound = torch.zeros(1, dtype=torch.float32, device=weight.device)
-
-    def refresh(self, stream):
-        w = self.weight
-        key = (w.data_ptr(), _ver(w))
-        if key != self.key:
-            if not w.is_contiguous() or w.dtype != torch.float32:
-                raise RuntimeError("bbdm_amd: conv weights must be contiguous fp32")
-            _lib.call("bbdm_conv_pack_weight_f32", w.data_ptr(), self.packed_f32.data_ptr(), self.cout, self.cin,
-                      self.cin_pad, 1, stream)
-            _zero_on(self.ubound, stream)
-            _lib.call("bbdm_absmax_f32", self.packed_f32.data_ptr(), self.packed_f32.numel(), self.ubound.data_ptr(), stream)
-            _lib.call("bbdm_gemm_h2p_pack_b_f32", self.packed_f32.data_ptr(), self.packed.data_ptr(), self.ubound.data_ptr(), 1.0, 1,
-                      self.cin_pad, self.cout, stream)
-            self.key = key
-
-
-class _RowL1Gain:
-    """(max over rows of sum |W[row, :]|, max |bias|) of a 1x1 conv / Linear as two device floats, refreshed with the weights: what
-    turns a bound of the layer's input into a bound of its output (csrc/groupnorm.hip: h2_rowl1_kernel / bbdm_h2_affine_bound_f32)."""
-
-    def __init__(self, weight, bias):
-        self.weight, self.bias = weight, bias
-        self.gain = torch.zeros(2, dtype=torch.float32, device=weight.device)
-        self.key = None
-
-    def refresh(self, stream):
-        w, b = self.weight, self.bias
-        key = (w.data_ptr(), _ver(w), None if b is None else (b.data_ptr(), _ver(b)))
-        if key != self.key:
-            if not w.is_contiguous() or w.dtype != torch.float32:
-                raise RuntimeError("bbdm_amd: conv weights must be contiguous fp32")
-            _lib.call("bbdm_h2_rowl1_f32", w.data_ptr(), None if b is None else b.data_ptr(), w.shape[0], w[0].numel(),
-                      self.gain.data_ptr(), stream)
-            self.key = key
-
-
-class _PackedDgradBf3:
-    """The transposed weight of a 1x1 conv / Linear in the three-bf16-plane layout of csrc/gemm_bf3.hip: the data gradient
-    dX = dY W as one more fp32-accurate GEMM on the BF16 matrix core (``packed``; the fp32 dgrad packing is the intermediate)."""
-
-    def __init__(self, weight: nn.Parameter, cout_in: int, planes=False):
-        """``planes``: the B planes of csrc/gemm_bf3p.hip (for bbdm_conv1x1_bf3q_f32) instead of gemm_bf3.hip's layout; "h": the
-        fp16-pair planes under the weights' exact maximum ``ubound`` (bbdm_conv1x1_h2q_f32; round 6)."""
-        self.weight = weight
-        self.cout, self.cin = weight.shape[0], weight.shape[1]
-        self.cout_in, self.planes = cout_in, planes
-        lib = _lib.load()
-        self.packed_f32 = torch.empty(lib.bbdm_conv_packed_dgrad_floats(self.cout, self.cin, cout_in, 1), dtype=torch.float32,
-                                      device=weight.device)
-        self.ubound = torch.zeros(1, dtype=torch.float32, device=weight.device) if planes == "h" else None
-        if planes == "h":
-            self.packed = torch.empty(lib.bbdm_gemm_h2p_b_bytes(1, cout_in, self.cin), dtype=torch.uint8, device=weight.device)
-        elif planes:
-            self.packed = torch.empty(lib.bbdm_gemm_bf3p_b_bytes(1, cout_in, self.cin), dtype=torch.uint8, device=weight.device)
-        else:
-            self.packed = torch.empty(lib.bbdm_gemm_bf3_packed_halfs(1, cout_in, self.cin), dtype=torch.int16, device=weight.device)
-        self.key = None
-
-    def refresh(self, stream):
-        w = self.weight
-        key = (w.data_ptr(), _ver(w))
-        if key != self.key:
-            _lib.call("bbdm_conv_pack_weight_dgrad_f32", w.data_ptr(), self.packed_f32.data_ptr(), self.cout, self.cin,
-                      self.cout_in, 1, stream)
-            if self.planes == "h":
-                _zero_on(self.ubound, stream)
-                _lib.call("bbdm_absmax_f32", self.packed_f32.data_ptr(), self.packed_f32.numel(), self.ubound.data_ptr(), stream)
-                _lib.call("bbdm_gemm_h2p_pack_b_f32", self.packed_f32.data_ptr(), self.packed.data_ptr(), self.ubound.data_ptr(), 1.0, 1,
-                          self.cout_in, self.cin, stream)
-            else:
-                _lib.call("bbdm_gemm_bf3p_pack_b_f32" if self.planes else "bbdm_gemm_bf3_pack_f32", self.packed_f32.data_ptr(),
-                          self.packed.data_ptr(), 1, self.cout_in, self.cin, stream)
-            self.key = key
-
-
-class _PackedDgrad:
-    """Packed transposed + flipped copy of a conv weight: the forward kernel run with it computes the data gradient."""
-
-    def __init__(self, weight: nn.Parameter, cout_in: int):
-        self.weight = weight
-        self.cout, self.cin = weight.shape[0], weight.shape[1]
-        self.ks = weight.shape[2] if weight.dim() == 4 else 1
-        self.cout_in = cout_in
-        n = _lib.load().bbdm_conv_packed_dgrad_floats(self.cout, self.cin, cout_in, self.ks)
-        self.packed = torch.empty(n, dtype=torch.float32, device=weight.device)
-        self.key = None
-
-    def refresh(self, stream):
-        w = self.weight
-        key = (w.data_ptr(), _ver(w))
-        if key != self.key:
-            _lib.call("bbdm_conv_pack_weight_dgrad_f32", w.data_ptr(), self.packed.data_ptr(), self.cout, self.cin,
-                      self.cout_in, self.ks, stream)
-            self.key = key
-
-
-class _PackedWinograd:
-    """G g G^T of one 3x3 conv weight in the batched-GEMM layout (``dgrad``: of the data-gradient convolution).  With
-    ``bf3`` the fp32 buffer is additionally split into the three bf16 planes csrc/gemm_bf3.hip takes; ``packed`` is then
-    that buffer (the op binds to bbdm_winograd_gemm_bf3_f32).  ``bf3 == "p"``: the planes in the fragment-unit layout of
-    csrc/gemm_bf3p.hip, whose A operand the input transform writes pre-split (bbdm_winograd_input_bf3p_f32 / _gemm_bf3p_f32)."""
-
-    def __init__(self, weight: nn.Parameter, bias: Optional[nn.Parameter], in_pad: int, m: int, dgrad: bool = False,
-                 bf3: bool = False, phases: bool = False):
-        self.weight, self.bias, self.dgrad, self.m, self.bf3 = weight, bias, dgrad, m, bf3
-        self.cout, self.cin = weight.shape[0], weight.shape[1]
-        self.ks, self.in_pad = 3, in_pad
-        lib = _lib.load()
-        # ``phases``: the layer is conv3x3(nearest x2 (x)); packed are its four phase filters, a conv Cin -> 4 Cout on x itself
-        # (bbdm_upsample_phase_weights_f32, BBDM_CONV_OUT_PHASES)
-        assert not (phases and dgrad)
-        self.phases = phases
-        self.w4 = torch.empty(4 * self.cout, self.cin, 3, 3, dtype=torch.float32, device=weight.device) if phases else None
-        self.out_ch = self.cin if dgrad else (4 * self.cout if phases else self.cout)
-        n = lib.bbdm_winograd_packed_floats(m, self.out_ch, in_pad)
-        # (the planes of gemm_bf3p.hip are written directly from the weights: no fp32 G g G^T tensor -- 4x the weights at m = 4 -- is kept)
-        self.fused_planes = bf3 == "p" and not phases and in_pad % 16 == 0
-        # bf3 == "h": two fp16 planes under the scale of max |U| (csrc/h2_split.h); the fp32 G g G^T tensor only exists while packing
-        self.packed_f32 = None if (self.fused_planes or bf3 == "h") else torch.empty(n, dtype=torch.float32, device=weight.device)
-        self._n_f32 = n
-        self.ubound = torch.zeros(1, dtype=torch.float32, device=weight.device) if bf3 == "h" else None
-        if bf3 == "h":
-            self.packed = torch.empty(lib.bbdm_gemm_h2p_b_bytes(wino_planes(m), in_pad, self.out_ch), dtype=torch.uint8,
-                                      device=weight.device)
-        elif bf3 == "p":
-            self.packed = torch.empty(lib.bbdm_gemm_bf3p_b_bytes(wino_planes(m), in_pad, self.out_ch), dtype=torch.uint8,
-                                      device=weight.device)
-        elif bf3:
-            nh = lib.bbdm_gemm_bf3_packed_halfs(wino_planes(m), in_pad, self.out_ch)
-            self.packed = torch.empty(nh, dtype=torch.int16, device=weight.device)
-        else:
-            self.packed = self.packed_f32
-        self.packed.cin_true = self.cout if dgrad else self.cin
-        self.key = None
-
-    def refresh(self, stream):
-        w = self.weight
-        key = (w.data_ptr(), _ver(w))
-        if key != self.key:
-            if not w.is_contiguous() or w.dtype != torch.float32:
-                raise RuntimeError("bbdm_amd: conv weights must be contiguous fp32")
-            if self.bf3 == "h":
-                # fp16-pair planes of U 2^e: e from ``ubound`` = the filter's largest tap (one small pass over the weights) times the gain
-                # of G . G^T, the factor the tile GEMM applies to the same pointer -- G g G^T goes straight into the planes
-                _zero_on(self.ubound, stream)
-                if self.phases:
-                    _lib.call("bbdm_upsample_phase_weights_f32", w.data_ptr(), self.w4.data_ptr(), self.cout, self.cin, stream)
-                    _lib.call("bbdm_absmax_f32", self.w4.data_ptr(), self.w4.numel(), self.ubound.data_ptr(), stream)
-                    tmp = torch.empty(self._n_f32, dtype=torch.float32, device=w.device)
-                    _lib.call("bbdm_winograd_pack_weight_f32", self.m, self.w4.data_ptr(), tmp.data_ptr(), 4 * self.cout, self.cin,
-                              self.in_pad, 0, stream)
-                    _lib.call("bbdm_gemm_h2p_pack_b_f32", tmp.data_ptr(), self.packed.data_ptr(), self.ubound.data_ptr(),
-                              float(_lib.load().bbdm_winograd_g_gain(self.m)), wino_planes(self.m), self.in_pad, self.out_ch, stream)
-                else:
-                    _lib.call("bbdm_absmax_f32", w.data_ptr(), w.numel(), self.ubound.data_ptr(), stream)
-                    _lib.call("bbdm_winograd_pack_weight_h2p_f32", self.m, w.data_ptr(), self.packed.data_ptr(), self.cout, self.cin,
-                              self.in_pad, 1 if self.dgrad else 0, self.ubound.data_ptr(), stream)
-                self.key = key
-                return
-            if self.phases:
-                _lib.call("bbdm_upsample_phase_weights_f32", w.data_ptr(), self.w4.data_ptr(), self.cout, self.cin, stream)
-                _lib.call("bbdm_winograd_pack_weight_f32", self.m, self.w4.data_ptr(), self.packed_f32.data_ptr(), 4 * self.cout,
-                          self.cin, self.in_pad, 0, stream)
-            elif self.fused_planes:
-                # G g G^T straight into the bf16 planes (the two launches below in one, without the fp32 tensor in between)
-                _lib.call("bbdm_winograd_pack_weight_bf3p_f32", self.m, w.data_ptr(), self.packed.data_ptr(), self.cout, self.cin,
-                          self.in_pad, 1 if self.dgrad else 0, stream)
-                self.key = key
-                return
-            else:
-                _lib.call("bbdm_winograd_pack_weight_f32", self.m, w.data_ptr(), self.packed_f32.data_ptr(), self.cout, self.cin,
-                          self.in_pad, 1 if self.dgrad else 0, stream)
-            if self.bf3:
-                _lib.call("bbdm_gemm_bf3p_pack_b_f32" if self.bf3 == "p" else "bbdm_gemm_bf3_pack_f32",
-                          self.packed_f32.data_ptr(), self.packed.data_ptr(), wino_planes(self.m), self.in_pad, self.out_ch, stream)
-            self.key = key
-
-
-def wino_planes(m: int) -> int:
-    """Transform points of Winograd tile ``m``: (m + 2)^2 for F(m x m, 3x3); m = 7 is F(7x7, 2x2) on the 8-point transform."""
-    return 64 if m == 7 else (m + 2) ** 2
 
 
 def wino_tiles(m: int, N: int, H: int, W: int) -> int:
@@ -1269,11 +973,8 @@ class _Plan:
         self.ops.append(rec)
         return rec
 
-    def _packed(self, cls, weight, *args, **kw):
-        return cls(weight, *args, **kw)
-
-    def _conv(self, mod, cin_pad) -> _PackedConv:
-        pc = self._packed(_PackedConv, mod.weight, mod.bias, cin_pad)
+    def _conv(self, mod, cin_pad, layout=False) -> _PackedConv:
+        pc = _PackedConv(mod.weight, mod.bias, cin_pad, layout)
         self.convs.append(pc)
         return pc
 
@@ -1382,7 +1083,7 @@ class _Plan:
     def _gn_bound(self, x: _View, gn, film_off):
         """Bound slot for GroupNorm(x) [-> FiLM] [-> SiLU] [-> average pool / nearest x2]: |value| <= |gamma (1 + s)| sqrt(n_g - 1) +
         |beta (1 + s) + t| whatever x holds (a z-score over n_g values is at most sqrt(n_g - 1); SiLU, averaging and copying do not
-        grow it).  Inference plans only; None when the fp16-pair planes are off."""
+        grow it).  Inference and training plans alike (_h2_on(1)); None when the fp16-pair planes are off."""
         if not self._h2_on(1) or gn is None:
             return None
         n_g = x.H * x.W * (x.C // self.GROUPS)
@@ -1446,7 +1147,7 @@ class _Plan:
         wm = self._winograd_ok(consumer, H, W, x.C)
         if not wm or wm == 8 or x.C % 16 or (x.C // self.GROUPS) % 2 or consumer.weight.shape[1] != x.C:
             return False                      # (m = 8: large layers only, no coefficient-folding input transform)
-        small = bool(m.gemm_bf3 and m.gemm_bf3p and m.winograd_small)
+        small = self._wino_small()
         cands = [(wm, H, W, cout)]
         if up == 2 and m.upsample_phases:         # conv3x3(nearest x2 (x)) may run as four phase filters on x itself
             wl = phase_filter_tile(self.N, x.H, x.W, x.C, 4 * cout, m.winograd, small, m.upsample_f72 and not self.training)
@@ -1473,9 +1174,12 @@ class _Plan:
         w = mod.weight
         if not self.m.winograd or w.dim() != 4 or w.shape[2] != 3 or (flags & ~6) != 0:
             return 0
-        return winograd_tile(self.N, H, W, cin_pad, w.shape[0], self.m.winograd,
-                             small=bool(self.m.gemm_bf3 and self.m.gemm_bf3p and self.m.winograd_small),
-                             allow8=self._allow8(2))
+        return winograd_tile(self.N, H, W, cin_pad, w.shape[0], self.m.winograd, small=self._wino_small(), allow8=self._allow8(2))
+
+    def _wino_small(self) -> bool:
+        """May small layers take F(2x2, 3x3) (``small`` of :func:`winograd_tile`)?  They run on the pre-split bf16x3 pipeline only."""
+        m = self.m
+        return bool(m.gemm_bf3 and m.gemm_bf3p and m.winograd_small)
 
     def _allow8(self, level: int) -> int:
         """F(8x8, 3x3) for this plan's forward / weight gradient (``level`` 2) or data gradient (1)?  Needs the pre-split bf16x3 pipeline.
@@ -1588,6 +1292,37 @@ class _Plan:
                        N, H, W, cout_y, None, 0, 0, None, 0, 0, *ks_tail)
             self._note_writer(dest, rec, 12)
 
+    def _conv1x1_form(self, pixels: int, cin: int, cout: int, bounded: bool):
+        """The matrix-core form of a plain 1x1 convolution / Linear (no fused producer, no flags; ``bounded``: its input carries a bound):
+        (entry point, plane layout of its weights, does it take the bound), or None = the direct kernel.  The order of the tests is
+        the policy."""
+        m = self.m
+        if bounded and self._conv1x1_h2_ok(pixels, cin, cout):
+            # wide layer whose input carries a bound: the fp16-pair planes (csrc/gemm_bf3p.hip: gemm_bf3q_pipe_kernel<NP = 2>)
+            return "bbdm_conv1x1_h2q_f32", "h", True
+        if m.gemm_bf3 and self.lib.bbdm_gemm_bf3_supported(pixels, cin, cout) and (pixels // 256) * -(-cout // 128) >= m.bf3_min_tiles:
+            # wide 1x1 convolutions / Linears (skip connections, qkv / proj_out, transformer projections): the fp32-accurate
+            # bf16x3 GEMM with bias + residual in its epilogue (csrc/gemm_bf3.hip); small problems keep the split-K f32 kernel
+            # ... on the pipelined kernel (csrc/gemm_bf3p.hip: gemm_bf3q_pipe_kernel, 200 - 214 instead of 165 - 192 TFLOP/s) where
+            # Cout fills 256-column tiles; its 128-column form loses to gemm_bf3.hip's 8-wave workgroups
+            if (-(-cout // 128) * 128) % 256 == 0:
+                return "bbdm_conv1x1_bf3q_f32", "p", False
+            return "bbdm_conv1x1_bf3_f32", True, False
+        if bounded and self._conv1x1_h2s_ok(pixels, cin, cout):
+            return "bbdm_conv1x1_h2s_f32", "h", True
+        if m.gemm_bf3 and m.conv1x1_small and cin % 64 == 0 and cout % 4 == 0:
+            # small 1x1 convolutions / Linears: bound by the length of a workgroup's chain of K steps, not by the matrix pipe -- the
+            # small-problem bf16x3 kernel (64 channels per step, one launch) instead of the split-K f32 kernel + its reduction pass
+            return "bbdm_conv1x1_bf3s_f32", "p", False
+        return None
+
+    def _emit_conv1x1(self, emit, entry: str, x: _View, pk, bias, residual, res_ld, dest: _View, pixels: int, cout: int, bound=None):
+        """One 1x1 convolution on the matrix core, forward or data gradient: ``pk.packed`` in the layout ``entry`` reads; ``bound`` (the
+        fp16-pair forms): the reference of the input's bound, which travels with the weights' own (``pk.ubound``)."""
+        name = entry if entry == "bbdm_conv1x1_bf3_f32" else _OpName("bbdm_conv1x1_bf3_f32", entry)
+        tail = () if bound is None else (bound, _TensorRef(pk.ubound))
+        return emit(name, x, x.ld, _TensorRef(pk.packed), bias, residual, res_ld, dest, dest.ld, pixels, x.C, cout, *tail)
+
     def _emit_conv(self, x: _View, mod, residual, dest: _View, res_ld: Optional[int] = None, flags: int = 0,
                    pre=None, upsample: bool = False):
         """``residual`` is an NHWC view, or (with flags & 2) a per-image [N][res_ld] tensor reference, or (flags & 4, Winograd path only)
@@ -1604,19 +1339,17 @@ class _Plan:
         if wm and upsample and self.m.upsample_phases and residual is None and flags == 0 and mod.weight.shape[1] == x.C:
             # conv3x3(nearest x2 (x)) = four phase filters on x (Cin -> 4 Cout): same GEMM work, the input transform and the GEMM's
             # A operand shrink 4x -- taken where x's own tile grid earns the same Winograd tile as the upsampled one
-            wl = phase_filter_tile(self.N, x.H, x.W, x.C, 4 * cout, self.m.winograd,
-                                   bool(self.m.gemm_bf3 and self.m.gemm_bf3p and self.m.winograd_small),
+            wl = phase_filter_tile(self.N, x.H, x.W, x.C, 4 * cout, self.m.winograd, self._wino_small(),
                                    self.m.upsample_f72 and not self.training)
             if wl == 7 and self._use_bf3(7, x.H, x.W, x.C, 4 * cout, h2=h2) not in ("p", "h"):
                 wl = 6                            # (F(7x7, 2x2) exists on the pre-split planes only)
             if wl >= min(wm, 6):               # (m = 8 at the upsampled size does not beat the phase filters' 4x smaller input transform)
-                pw = self._packed(_PackedWinograd, mod.weight, mod.bias, x.C, wl, bf3=self._use_bf3(wl, x.H, x.W, x.C, 4 * cout, h2=h2),
-                                  phases=True)
+                pw = _PackedWinograd(mod.weight, mod.bias, x.C, wl, bf3=self._use_bf3(wl, x.H, x.W, x.C, 4 * cout, h2=h2), phases=True)
                 self.convs.append(pw)
                 self._emit_winograd(x, x.C, pw, pre, False, x.H, x.W, None, 0, dest, 0)
                 return
         if wm:
-            pw = self._packed(_PackedWinograd, mod.weight, mod.bias, x.C, wm, bf3=self._use_bf3(
+            pw = _PackedWinograd(mod.weight, mod.bias, x.C, wm, bf3=self._use_bf3(
                 wm, H, W, x.C, cout, keeps_V=self._keeps_V(wm, H, W, x.C, mod.weight.shape[1], cout, upsample, False), h2=h2))
             self.convs.append(pw)
             self._emit_winograd(x, x.C, pw, pre, upsample, H, W, residual, res_ld, dest, flags)
@@ -1628,44 +1361,13 @@ class _Plan:
             raise RuntimeError("bbdm_amd: a coefficient-folding producer reached a layer that is not a Winograd layer on the pre-split planes")
         ks = mod.weight.shape[2] if mod.weight.dim() == 4 else 1
         pixels = self.N * x.H * x.W
-        xb = getattr(pre, "h2", None)
-        if (ks == 1 and xb is not None and (pre is None or pre[0] is None) and flags == 0 and self._conv1x1_h2_ok(pixels, x.C, cout)):
-            # wide 1x1 convolution whose input carries a bound: the fp16-pair planes (csrc/gemm_bf3p.hip: gemm_bf3q_pipe_kernel<NP = 2>)
-            pb = self._packed(_PackedConvH2q, mod.weight, mod.bias, x.C)
-            self.convs.append(pb)
-            rec = self._op(_OpName("bbdm_conv1x1_bf3_f32", "bbdm_conv1x1_h2q_f32"), x, x.ld, _TensorRef(pb.packed), self._pref(pb.bias),
-                           residual, res_ld, dest, dest.ld, pixels, x.C, cout, xb, _TensorRef(pb.ubound))
-            self._note_writer(dest, rec, None)
-            return
-        if (ks == 1 and self.m.gemm_bf3 and (pre is None or pre[0] is None) and flags == 0
-                and self.lib.bbdm_gemm_bf3_supported(pixels, x.C, cout)
-                and (pixels // 256) * -(-cout // 128) >= self.m.bf3_min_tiles):
-            # wide 1x1 convolutions / Linears (skip connections, qkv / proj_out, transformer projections): the fp32-accurate
-            # bf16x3 GEMM with bias + residual in its epilogue (csrc/gemm_bf3.hip); small problems keep the split-K f32 kernel
-            # ... on the pipelined kernel (csrc/gemm_bf3p.hip: gemm_bf3q_pipe_kernel, 200 - 214 instead of 165 - 192 TFLOP/s) where
-            # Cout fills 256-column tiles; its 128-column form loses to gemm_bf3.hip's 8-wave workgroups
-            q = (-(-cout // 128) * 128) % 256 == 0
-            pb = self._packed(_PackedConvBf3q if q else _PackedConvBf3, mod.weight, mod.bias, x.C)
-            self.convs.append(pb)
-            rec = self._op(_OpName("bbdm_conv1x1_bf3_f32", "bbdm_conv1x1_bf3q_f32") if q else "bbdm_conv1x1_bf3_f32", x, x.ld,
-                           _TensorRef(pb.packed), self._pref(pb.bias), residual, res_ld, dest, dest.ld, pixels, x.C, cout)
-            self._note_writer(dest, rec, None)
-            return
-        if (ks == 1 and xb is not None and (pre is None or pre[0] is None) and flags == 0 and self._conv1x1_h2s_ok(pixels, x.C, cout)):
-            pb = self._packed(_PackedConvH2q, mod.weight, mod.bias, x.C)
-            self.convs.append(pb)
-            rec = self._op(_OpName("bbdm_conv1x1_bf3_f32", "bbdm_conv1x1_h2s_f32"), x, x.ld, _TensorRef(pb.packed), self._pref(pb.bias),
-                           residual, res_ld, dest, dest.ld, pixels, x.C, cout, xb, _TensorRef(pb.ubound))
-            self._note_writer(dest, rec, None)
-            return
-        if (ks == 1 and self.m.gemm_bf3 and self.m.conv1x1_small and (pre is None or pre[0] is None) and flags == 0
-                and x.C % 64 == 0 and cout % 4 == 0):
-            # small 1x1 convolutions / Linears: bound by the length of a workgroup's chain of K steps, not by the matrix pipe -- the
-            # small-problem bf16x3 kernel (64 channels per step, one launch) instead of the split-K f32 kernel + its reduction pass
-            pb = self._packed(_PackedConvBf3q, mod.weight, mod.bias, x.C)
-            self.convs.append(pb)
-            rec = self._op(_OpName("bbdm_conv1x1_bf3_f32", "bbdm_conv1x1_bf3s_f32"), x, x.ld, _TensorRef(pb.packed), self._pref(pb.bias),
-                           residual, res_ld, dest, dest.ld, pixels, x.C, cout)
+        form = self._conv1x1_form(pixels, x.C, cout, getattr(pre, "h2", None) is not None) \
+            if (ks == 1 and (pre is None or pre[0] is None) and flags == 0) else None
+        if form is not None:
+            entry, layout, bounded = form
+            pb = self._conv(mod, x.C, layout)
+            rec = self._emit_conv1x1(self._op, entry, x, pb, self._pref(pb.bias), residual, res_ld, dest, pixels, cout,
+                                     pre.h2 if bounded else None)
             self._note_writer(dest, rec, None)
             return
         pc = self._conv(mod, x.C)
@@ -2116,8 +1818,7 @@ class _Plan:
             if not need_dx:
                 return None
             dx = self._tmp(dx_name, N, x_in.H, x_in.W, x_in.C)
-            wm = (winograd_tile(N, x_in.H, x_in.W, dy.C, x_in.C, m.winograd,
-                                small=bool(m.gemm_bf3 and m.gemm_bf3p and m.winograd_small), allow8=self._allow8(1))
+            wm = (winograd_tile(N, x_in.H, x_in.W, dy.C, x_in.C, m.winograd, small=self._wino_small(), allow8=self._allow8(1))
                   if (m.winograd and ks == 3 and w.dim() == 4 and x_in.C == cin) else 0)
             if wm:
                 mode = self._use_bf3(wm, x_in.H, x_in.W, dy.C, x_in.C, h2=self._h2_on(2) and dy.C % 4 == 0 and dy.ld % 4 == 0)
@@ -2131,21 +1832,19 @@ class _Plan:
             if (ks == 1 and x_in.C == cin and self._h2_on(2) and getattr(m, "conv1x1_h2", True) and dy.C % 16 == 0 and dy.ld % 4 == 0
                     and x_in.C % 4 == 0 and (pixels // 256) * -(-x_in.C // 128) >= m.bf3_min_tiles):
                 # wide 1x1 layers on the fp16 pair: dX = dY W with dY under its measured maximum (as the 3x3 layers' data gradient)
-                pk = _PackedDgradBf3(w, dy.C, planes="h")
+                pk = _PackedConv(w, None, dy.C, "h", dgrad=True)
                 self.dconvs.append(pk)
                 dy_ref[0] = dy_ref[0] or self._dy_bound(dy)
-                self._bop(_OpName("bbdm_conv1x1_bf3_f32", "bbdm_conv1x1_h2q_f32"), dy, dy.ld, _TensorRef(pk.packed), None, None, 0, dx,
-                          dx.ld, pixels, dy.C, x_in.C, dy_ref[0], _TensorRef(pk.ubound))
+                self._emit_conv1x1(self._bop, "bbdm_conv1x1_h2q_f32", dy, pk, None, None, 0, dx, pixels, x_in.C, dy_ref[0])
                 return dx
             if (ks == 1 and m.gemm_bf3 and x_in.C == cin and lib.bbdm_gemm_bf3_supported(pixels, dy.C, x_in.C)
                     and (pixels // 256) * -(-x_in.C // 128) >= m.bf3_min_tiles):
                 q = (-(-x_in.C // 128) * 128) % 256 == 0
-                pk = _PackedDgradBf3(w, dy.C, planes=q)  # wide 1x1 layers: dX = dY W on the bf16x3 GEMM, like their forward
+                pk = _PackedConv(w, None, dy.C, "p" if q else True, dgrad=True)  # wide 1x1 layers: dX = dY W on the bf16x3 GEMM, like their forward
                 self.dconvs.append(pk)
-                self._bop(_OpName("bbdm_conv1x1_bf3_f32", "bbdm_conv1x1_bf3q_f32") if q else "bbdm_conv1x1_bf3_f32", dy, dy.ld,
-                          _TensorRef(pk.packed), None, None, 0, dx, dx.ld, pixels, dy.C, x_in.C)
+                self._emit_conv1x1(self._bop, "bbdm_conv1x1_bf3q_f32" if q else "bbdm_conv1x1_bf3_f32", dy, pk, None, None, 0, dx, pixels, x_in.C)
                 return dx
-            pk = _PackedDgrad(w, dy.C)
+            pk = _PackedConv(w, None, dy.C, dgrad=True)
             self.dconvs.append(pk)
             self._conv_ws_need = max(self._conv_ws_need,
                                      lib.bbdm_conv_splitk_workspace_floats(N, x_in.H, x_in.W, dy.C, x_in.C, ks))
@@ -2164,7 +1863,7 @@ class _Plan:
 
         f32 = dict(dtype=torch.float32, device=dev)
         self.dfilm = torch.zeros(N, self.film_total, **f32)
-        self.dconvs: List[_PackedDgrad] = []
+        self.dconvs: List[_PackedConv] = []
         self._padded_wgrads: List[tuple] = []
         self._ws_f = _LateTensor()
         self._ws_f_side, self._ws_f_side_floats = _LateTensor(), _LateInt()
@@ -2335,7 +2034,7 @@ class _Plan:
                 conv_bwd(conv, x, dout, False, "DX0")
                 # d input (only when x / context require grad, e.g. a trainable SpatialRescaler context): own op list
                 main, self.bops = self.bops, []
-                pk = _PackedDgrad(conv.weight, dout.C)
+                pk = _PackedConv(conv.weight, None, dout.C, dgrad=True)
                 self.dconvs.append(pk)
                 self.dx0 = self._tmp("DX0", N, x.H, x.W, x.C)
                 self._bop("bbdm_conv2d_nhwc_f32", dout, dout.ld, _TensorRef(pk.packed), None, None, 0, self.dx0,
