@@ -6,7 +6,7 @@ hand-written HIP kernels behind a C-ABI (include/bbdm_hip.h), exposed through dr
 from .model import BrownianBridgeModel, LatentBrownianBridgeModel, bridge_schedule, philox_normal  # noqa: F401
 from .unet import UNetModel  # noqa: F401
 from .cond_stage import SpatialRescaler  # noqa: F401
-from .sampler import BridgeSampler  # noqa: F401
+from .sampler import BridgeSampler, SamplingParams  # noqa: F401
 
 __all__ = ["BrownianBridgeModel", "LatentBrownianBridgeModel", "UNetModel", "SpatialRescaler", "bridge_schedule",
-           "BridgeSampler", "philox_normal"]
+           "BridgeSampler", "SamplingParams", "philox_normal"]

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBDM_HIP_LIB overrides the library path (A/B runs of kernel variants); the default is the in-tree build
 LIB_PATH = os.environ.get("BBDM_HIP_LIB") or os.path.join(_HERE, "libbbdm_hip.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _P = c_void_p
 # name -> (restype, argtypes); must list every symbol of include/bbdm_hip.h (tests/test_abi.py checks it)
@@ -82,6 +82,10 @@ SIGNATURES = {
                                           _P, _P, _P, c_int, c_int, _P]),
     "bbdm_bb_p_sample_step_batched_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int, c_int,
                                                   _P, _P, _P, c_int, c_int, _P]),
+    # eta and the clip decision per image (ABI 29): float eta[N] in place of (eta, clip); bit 2 of the flag word = clip
+    "bbdm_bb_p_sample_step_requests_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, _P]),
+    "bbdm_bb_p_sample_step_requests_philox_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int,
+                                                          c_int, _P]),
     # seed-addressed noise (ABI 27; csrc/philox.h)
     "bbdm_philox_normal_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "bbdm_philox_raw_u32": (c_int, [_P, _P, c_int, _P]),

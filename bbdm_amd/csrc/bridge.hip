@@ -83,21 +83,43 @@ __global__ void p_step_kernel(const float* __restrict__ x_t, const float* __rest
     }
 }
 
+// Where a per-image launch takes eta and the clip decision of image n from -- the P of the two kernels below.
+// UniformParams: one launch argument each, and the flag word is the state (the kernel arguments of the *_batched_ / *_philox_ entry
+// points, unchanged).  RequestParams (the *_requests_* entry points): eta[n] from a device array, read only by an image that takes a
+// step with noise; bits 0-1 of the flag word are the state and bit 2 says "clip this image".
+struct UniformParams {
+    float eta_;
+    int clip_;
+    __device__ __forceinline__ int64_t state(int64_t flag) const { return flag; }
+    __device__ __forceinline__ float eta(int) const { return eta_; }
+    __device__ __forceinline__ int clip(int64_t) const { return clip_; }
+};
+
+struct RequestParams {
+    const float* eta_;
+    __device__ __forceinline__ int64_t state(int64_t flag) const { return flag & 3; }
+    __device__ __forceinline__ float eta(int n) const { return eta_[n]; }
+    __device__ __forceinline__ int clip(int64_t flag) const { return (int)(flag >> 2) & 1; }
+};
+
 // p_step_kernel with a (step, next step, flag) per image: one image per blockIdx.y, so the coefficients are evaluated once
-// per thread and image.  flag 0: a step with noise, 1: the last step (x_next = x0_recon, no noise read), 2: an inactive slot
-// (nothing read or written).  The float expressions are p_step_kernel's, in the same order: an image whose (t, t_next, last)
-// equals a scalar launch's gets the scalar kernel's bits.
+// per thread and image.  State 0: a step with noise, 1: the last step (x_next = x0_recon, no noise read), 2: an inactive slot
+// (nothing read or written).  The float expressions are p_step_kernel's, in the same order: an image whose (t, t_next, last, eta,
+// clip) equals a scalar launch's gets the scalar kernel's bits.
+template <class P>
 __global__ void p_step_batched_kernel(const float* __restrict__ x_t, const float* __restrict__ y,
                                       const float* __restrict__ pred, const float* __restrict__ noise,
                                       const float* __restrict__ m_tab, const float* __restrict__ var_tab,
                                       const int64_t* __restrict__ t_arr, const int64_t* __restrict__ t_next_arr,
-                                      const int64_t* __restrict__ flag_arr, float eta, int clip, int objective,
+                                      const int64_t* __restrict__ flag_arr, P params, int objective,
                                       float* __restrict__ x_next, float* __restrict__ x0_recon,
                                       float* __restrict__ x_next_alias, int per_sample) {
     const int n = blockIdx.y;
     const int64_t flag = flag_arr[n];
-    if (flag == 2) return;
-    const int is_last = flag == 1;
+    const int64_t state = params.state(flag);
+    if (state == 2) return;
+    const int is_last = state == 1;
+    const int clip = params.clip(flag);
     const int64_t t = t_arr[n];
     const float m_t = m_tab[t], var_t = var_tab[t];
     const float sig_obj = sqrtf(var_t);
@@ -109,7 +131,7 @@ __global__ void p_step_batched_kernel(const float* __restrict__ x_t, const float
         const float a = (1.f - m_t) * (1.f - m_t);
         const float b = (1.f - m_nt) * (1.f - m_nt);
         const float sigma2 = (var_t - var_nt * a / b) * var_nt / var_t;
-        sigma_t = sqrtf(sigma2) * eta;
+        sigma_t = sqrtf(sigma2) * params.eta(n);
         coef = sqrtf((var_nt - sigma2) / var_t);
     }
     const size_t base = (size_t)n * per_sample;
@@ -185,21 +207,23 @@ __global__ void philox_raw_kernel(const uint32_t* __restrict__ ck, uint32_t* __r
 // p_step_batched_kernel with the noise generated in registers (domain 0): the same (t, t_next, flag) per image and the same float
 // expressions in the same order, so it equals p_step_batched_kernel fed philox_normal_kernel's tensor bit for bit.  Last-step and
 // inactive images generate nothing.
-template <bool VEC>
+template <bool VEC, class P>
 __global__ void __launch_bounds__(256) p_step_philox_kernel(const float* __restrict__ x_t, const float* __restrict__ y,
                                                             const float* __restrict__ pred, const int64_t* __restrict__ seed_arr,
                                                             const int64_t* __restrict__ ordinal_arr,
                                                             const float* __restrict__ m_tab, const float* __restrict__ var_tab,
                                                             const int64_t* __restrict__ t_arr,
                                                             const int64_t* __restrict__ t_next_arr,
-                                                            const int64_t* __restrict__ flag_arr, float eta, int clip,
+                                                            const int64_t* __restrict__ flag_arr, P params,
                                                             int objective, float* __restrict__ x_next,
                                                             float* __restrict__ x0_recon, float* __restrict__ x_next_alias,
                                                             int per_sample) {
     const int n = blockIdx.y;
     const int64_t flag = flag_arr[n];
-    if (flag == 2) return;
-    const int is_last = flag == 1;
+    const int64_t state = params.state(flag);
+    if (state == 2) return;
+    const int is_last = state == 1;
+    const int clip = params.clip(flag);
     const int64_t t = t_arr[n];
     const float m_t = m_tab[t], var_t = var_tab[t];
     const float sig_obj = sqrtf(var_t);
@@ -212,7 +236,7 @@ __global__ void __launch_bounds__(256) p_step_philox_kernel(const float* __restr
         const float a = (1.f - m_t) * (1.f - m_t);
         const float b = (1.f - m_nt) * (1.f - m_nt);
         const float sigma2 = (var_t - var_nt * a / b) * var_nt / var_t;
-        sigma_t = sqrtf(sigma2) * eta;
+        sigma_t = sqrtf(sigma2) * params.eta(n);
         coef = sqrtf((var_nt - sigma2) / var_t);
         seed = seed_arr[n];
         ordinal = ordinal_arr[n];
@@ -351,6 +375,45 @@ inline dim3 group_grid(int N, int per_sample) {
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// The checks and the launch shared by the uniform and the per-request entry point of each per-image kernel (P as above).
+template <class P>
+int launch_p_step_batched(const char* what, const float* x_t, const float* y, const float* pred, const float* noise,
+                          const float* m_t, const float* variance_t, const int64_t* t, const int64_t* t_next,
+                          const int64_t* flag, P params, int objective, float* x_next, float* x0_recon, float* x_next_alias,
+                          int N, int per_sample, void* stream) {
+    BBDM_REQUIRE(x_t && y && pred && noise && m_t && variance_t && t && t_next && flag && x_next && x0_recon,
+                 "%s: null pointer", what);
+    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "%s: bad args", what);
+    const size_t b = ((size_t)per_sample + 255) / 256;
+    const unsigned bx = (unsigned)(b > 2048 ? 2048 : b);
+    hipLaunchKernelGGL(p_step_batched_kernel<P>, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x_t, y, pred, noise,
+                       m_t, variance_t, t, t_next, flag, params, objective, x_next, x0_recon, x_next_alias, per_sample);
+    BBDM_CHECK_LAUNCH(what);
+    return BBDM_OK;
+}
+
+template <class P>
+int launch_p_step_philox(const char* what, const float* x_t, const float* y, const float* pred, const int64_t* seed,
+                         const int64_t* ordinal, const float* m_t, const float* variance_t, const int64_t* t,
+                         const int64_t* t_next, const int64_t* flag, P params, int objective, float* x_next, float* x0_recon,
+                         float* x_next_alias, int N, int per_sample, void* stream) {
+    BBDM_REQUIRE(x_t && y && pred && seed && ordinal && m_t && variance_t && t && t_next && flag && x_next && x0_recon,
+                 "%s: null pointer", what);
+    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "%s: bad args", what);
+    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32), "%s: per_sample / 4 must fit the 32-bit counter word", what);
+    const dim3 grid = group_grid(N, per_sample);
+    const bool vec = per_sample % 4 == 0 && aligned16(x_t) && aligned16(y) && aligned16(pred) && aligned16(x_next) &&
+                     aligned16(x0_recon) && aligned16(x_next_alias);
+    if (vec)
+        hipLaunchKernelGGL((p_step_philox_kernel<true, P>), grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal,
+                           m_t, variance_t, t, t_next, flag, params, objective, x_next, x0_recon, x_next_alias, per_sample);
+    else
+        hipLaunchKernelGGL((p_step_philox_kernel<false, P>), grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal,
+                           m_t, variance_t, t, t_next, flag, params, objective, x_next, x0_recon, x_next_alias, per_sample);
+    BBDM_CHECK_LAUNCH(what);
+    return BBDM_OK;
+}
+
 }  // namespace
 
 extern "C" int bbdm_bb_q_sample_f32(const float* x0, const float* y, const float* noise, const int64_t* t,
@@ -397,15 +460,18 @@ extern "C" int bbdm_bb_p_sample_step_batched_f32(const float* x_t, const float* 
                                                  const int64_t* t_next, const int64_t* flag, float eta, int clip, int objective,
                                                  float* x_next, float* x0_recon, float* x_next_alias, int N, int per_sample,
                                                  void* stream) {
-    BBDM_REQUIRE(x_t && y && pred && noise && m_t && variance_t && t && t_next && flag && x_next && x0_recon,
-                 "p_sample_step_batched: null pointer");
-    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "p_sample_step_batched: bad args");
-    const size_t b = ((size_t)per_sample + 255) / 256;
-    const unsigned bx = (unsigned)(b > 2048 ? 2048 : b);
-    hipLaunchKernelGGL(p_step_batched_kernel, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x_t, y, pred, noise,
-                       m_t, variance_t, t, t_next, flag, eta, clip, objective, x_next, x0_recon, x_next_alias, per_sample);
-    BBDM_CHECK_LAUNCH("p_sample_step_batched");
-    return BBDM_OK;
+    return launch_p_step_batched("p_sample_step_batched", x_t, y, pred, noise, m_t, variance_t, t, t_next, flag,
+                                 UniformParams{eta, clip}, objective, x_next, x0_recon, x_next_alias, N, per_sample, stream);
+}
+
+extern "C" int bbdm_bb_p_sample_step_requests_f32(const float* x_t, const float* y, const float* pred, const float* noise,
+                                                  const float* m_t, const float* variance_t, const int64_t* t,
+                                                  const int64_t* t_next, const int64_t* flag, const float* eta, int objective,
+                                                  float* x_next, float* x0_recon, float* x_next_alias, int N, int per_sample,
+                                                  void* stream) {
+    BBDM_REQUIRE(eta, "p_sample_step_requests: null eta");
+    return launch_p_step_batched("p_sample_step_requests", x_t, y, pred, noise, m_t, variance_t, t, t_next, flag,
+                                 RequestParams{eta}, objective, x_next, x0_recon, x_next_alias, N, per_sample, stream);
 }
 
 extern "C" int bbdm_philox_normal_f32(float* out, const int64_t* seed, const int64_t* ordinal, int domain, int N,
@@ -436,22 +502,19 @@ extern "C" int bbdm_bb_p_sample_step_philox_f32(const float* x_t, const float* y
                                                 const int64_t* t, const int64_t* t_next, const int64_t* flag, float eta,
                                                 int clip, int objective, float* x_next, float* x0_recon, float* x_next_alias,
                                                 int N, int per_sample, void* stream) {
-    BBDM_REQUIRE(x_t && y && pred && seed && ordinal && m_t && variance_t && t && t_next && flag && x_next && x0_recon,
-                 "p_sample_step_philox: null pointer");
-    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "p_sample_step_philox: bad args");
-    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32),
-                 "p_sample_step_philox: per_sample / 4 must fit the 32-bit counter word");
-    const dim3 grid = group_grid(N, per_sample);
-    const bool vec = per_sample % 4 == 0 && aligned16(x_t) && aligned16(y) && aligned16(pred) && aligned16(x_next) &&
-                     aligned16(x0_recon) && aligned16(x_next_alias);
-    if (vec)
-        hipLaunchKernelGGL(p_step_philox_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal, m_t,
-                           variance_t, t, t_next, flag, eta, clip, objective, x_next, x0_recon, x_next_alias, per_sample);
-    else
-        hipLaunchKernelGGL(p_step_philox_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal, m_t,
-                           variance_t, t, t_next, flag, eta, clip, objective, x_next, x0_recon, x_next_alias, per_sample);
-    BBDM_CHECK_LAUNCH("p_sample_step_philox");
-    return BBDM_OK;
+    return launch_p_step_philox("p_sample_step_philox", x_t, y, pred, seed, ordinal, m_t, variance_t, t, t_next, flag,
+                                UniformParams{eta, clip}, objective, x_next, x0_recon, x_next_alias, N, per_sample, stream);
+}
+
+extern "C" int bbdm_bb_p_sample_step_requests_philox_f32(const float* x_t, const float* y, const float* pred,
+                                                         const int64_t* seed, const int64_t* ordinal, const float* m_t,
+                                                         const float* variance_t, const int64_t* t, const int64_t* t_next,
+                                                         const int64_t* flag, const float* eta, int objective, float* x_next,
+                                                         float* x0_recon, float* x_next_alias, int N, int per_sample,
+                                                         void* stream) {
+    BBDM_REQUIRE(eta, "p_sample_step_requests_philox: null eta");
+    return launch_p_step_philox("p_sample_step_requests_philox", x_t, y, pred, seed, ordinal, m_t, variance_t, t, t_next, flag,
+                                RequestParams{eta}, objective, x_next, x0_recon, x_next_alias, N, per_sample, stream);
 }
 
 extern "C" int bbdm_bb_q_sample_philox_f32(const float* x0, const float* y, const int64_t* seed, const int64_t* ordinal,

@@ -330,6 +330,17 @@ int bbdm_bb_p_sample_step_batched_f32(const float* x_t, const float* y, const fl
                                       const float* m_t, const float* variance_t, const int64_t* t, const int64_t* t_next,
                                       const int64_t* flag, float eta, int clip, int objective, float* x_next,
                                       float* x0_recon, float* x_next_alias, int N, int per_sample, void* stream);
+/* bbdm_bb_p_sample_step_batched_f32 with eta and the clip decision per image (ABI 29; per-request sampling parameters in
+ * bbdm_amd/sampler.py).  Replaces what the reference fixes per model or per call: self.eta (BrownianBridgeModel.py:195) and
+ * the clip_denoised argument of p_sample (:172, :178-179, :187-188).  eta: float[N] on the device, read only by an image that takes a
+ * step with noise (not by a last-step or inactive image).  flag[n]: bits 0-1 the state of the batched entry point (0 a step
+ * with noise, 1 the last step, 2 inactive; 3 is reserved), bit 2 set = clamp this image's x0_recon to +-1; higher bits are
+ * ignored.  One kernel template serves both entry points: an image at (t, t_next, last, eta, clip) gets the bits of
+ * bbdm_bb_p_sample_step_f32 run on it alone, and uniform parameters give bbdm_bb_p_sample_step_batched_f32's result. */
+int bbdm_bb_p_sample_step_requests_f32(const float* x_t, const float* y, const float* pred, const float* noise,
+                                       const float* m_t, const float* variance_t, const int64_t* t, const int64_t* t_next,
+                                       const int64_t* flag, const float* eta, int objective, float* x_next,
+                                       float* x0_recon, float* x_next_alias, int N, int per_sample, void* stream);
 /* ---- seed-addressed noise (ABI 27; csrc/philox.h, DESIGN.md "Seed-addressed noise") -----------------------------------
  * Standard normals as a function of (seed, ordinal, domain, element): Philox4x32-10 with key = seed[n] (lo32, hi32) and
  * counter = (e / 4, ordinal[n] lo32, ordinal[n] hi32, domain), e the element's flat index inside image n; the four output
@@ -353,6 +364,15 @@ int bbdm_bb_p_sample_step_philox_f32(const float* x_t, const float* y, const flo
                                      const int64_t* t_next, const int64_t* flag, float eta, int clip, int objective,
                                      float* x_next, float* x0_recon, float* x_next_alias, int N, int per_sample,
                                      void* stream);
+/* bbdm_bb_p_sample_step_philox_f32 with eta and the clip decision per image (ABI 29): the self.eta of
+ * BrownianBridgeModel.py:195 and the clip_denoised of :172, :178-179, :187-188 as float eta[N] and bit 2 of flag[n], encoded as for
+ * bbdm_bb_p_sample_step_requests_f32.  Same two paths (128-bit / element accesses), same noise: it equals
+ * bbdm_bb_p_sample_step_requests_f32 fed bbdm_philox_normal_f32's tensor bit for bit. */
+int bbdm_bb_p_sample_step_requests_philox_f32(const float* x_t, const float* y, const float* pred, const int64_t* seed,
+                                              const int64_t* ordinal, const float* m_t, const float* variance_t,
+                                              const int64_t* t, const int64_t* t_next, const int64_t* flag, const float* eta,
+                                              int objective, float* x_next, float* x0_recon, float* x_next_alias, int N,
+                                              int per_sample, void* stream);
 /* bbdm_bb_q_sample_f32 with `noise` replaced by the per-image (seed, ordinal) of domain 1; for objective 'noise' the
  * target is the generated value. */
 int bbdm_bb_q_sample_philox_f32(const float* x0, const float* y, const int64_t* seed, const int64_t* ordinal,
