@@ -7,6 +7,7 @@ from .model import BrownianBridgeModel, LatentBrownianBridgeModel, bridge_schedu
 from .unet import UNetModel  # noqa: F401
 from .cond_stage import SpatialRescaler  # noqa: F401
 from .sampler import BridgeSampler, SamplingParams  # noqa: F401
+from .optim import EMA, FusedAdam, FusedRMSprop, FusedSGD, get_optimizer  # noqa: F401
 
 __all__ = ["BrownianBridgeModel", "LatentBrownianBridgeModel", "UNetModel", "SpatialRescaler", "bridge_schedule",
-           "BridgeSampler", "SamplingParams", "philox_normal"]
+           "BridgeSampler", "SamplingParams", "philox_normal", "FusedAdam", "FusedSGD", "FusedRMSprop", "EMA", "get_optimizer"]

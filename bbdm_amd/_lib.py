@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBDM_HIP_LIB overrides the library path (A/B runs of kernel variants); the default is the in-tree build
 LIB_PATH = os.environ.get("BBDM_HIP_LIB") or os.path.join(_HERE, "libbbdm_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _P = c_void_p
 # name -> (restype, argtypes); must list every symbol of include/bbdm_hip.h (tests/test_abi.py checks it)
@@ -184,6 +184,13 @@ SIGNATURES = {
     "bbdm_adam_ema_step_clip_f32": (c_int, [_P, c_int, c_int, c_double, c_double, c_double, c_double, c_double,
                                             ctypes.c_longlong, c_int, c_double, _P, c_int, _P]),
     "bbdm_grad_scale_f32": (c_int, [_P, c_int, _P, _P]),
+    # SGD / RMSprop on the same chunk table (ABI 30; csrc/optim.hip)
+    "bbdm_sgd_ema_step_f32": (c_int, [_P, c_int, c_double, c_double, c_double, c_double, c_int, c_int, c_int, c_double, _P]),
+    "bbdm_sgd_ema_step_clip_f32": (c_int, [_P, c_int, c_double, c_double, c_double, c_double, c_int, c_int, c_int, c_double,
+                                           _P, c_int, _P]),
+    "bbdm_rmsprop_ema_step_f32": (c_int, [_P, c_int, c_double, c_double, c_double, c_double, c_double, c_int, c_double, _P]),
+    "bbdm_rmsprop_ema_step_clip_f32": (c_int, [_P, c_int, c_double, c_double, c_double, c_double, c_double, c_int, c_double,
+                                               _P, c_int, _P]),
     "bbdm_set_option": (c_int, [c_char_p, c_int]),              # header: "options" (tests / tools A-B runs)
     "bbdm_get_option": (c_int, [c_char_p, _P]),
 }

@@ -38,6 +38,7 @@
 //   adam_ema_kernel<true> g * coef (one rounding, as grads.mul_(coef)) in front of adam_one; ok == 0 under skip_nonfinite: no Adam update
 //                        (the EMA part still runs, as the runner's ema.update would).
 //   grad_scale_kernel    g *= coef (the standalone clip_grad_norm_).
+//   rule_ema_kernel      the SGD and RMSprop rules (runners/utils.py:52-55) with the same mapping, clip buffer and EMA part: below.
 #include "common.h"
 #include "stats_acc.h"
 
@@ -129,6 +130,115 @@ __global__ void __launch_bounds__(256) adam_ema_kernel(const OptArgs a) {
             }
             if (ema) s[i] = a.ema_mode == 1 ? a.ema_c * pv + a.ema_decay * s[i] : pv;
         }
+    }
+}
+
+// ---- the two other update rules of runners/utils.py:48-57 (RMSProp, SGD) on the same chunk table (ABI 30) ----------------------------
+// torch's single-tensor formulas (_single_tensor_sgd / _single_tensor_rmsprop), operation by operation.  An add with a Python-number
+// alpha (grad.add(param, alpha=wd), buf.add_(grad, alpha=1 - dampening), param.add_(grad, alpha=-lr)) is ONE rounding in ATen's CPU
+// kernels: fmaf here, as adam_one does for the weight decay; addcmul / addcdiv are written as adam_one writes them.
+//   SGD      g' = g + wd * p;  buf = first ? g' : momentum * buf + (1 - dampening) * g';  g' = nesterov ? g' + momentum * buf : buf;
+//            p = p - lr * g'                                                  (the buf lines only with momentum != 0)
+//   RMSprop  g' = g + wd * p;  sq = alpha * sq + (1 - alpha) * g' * g';  avg = sqrt(sq) + eps;
+//            momentum != 0: buf = momentum * buf + g' / avg, p = p - lr * buf;  else p = p - lr * (g' / avg)
+// The table's exp_avg slot carries the momentum buffer (NULL without momentum), the exp_avg_sq slot RMSprop's square_avg (NULL for SGD).
+enum { RULE_SGD = 0, RULE_RMSPROP = 1 };
+
+struct RuleArgs {
+    const BbdmOptChunk* table;
+    float lr, wd, mom, damp_c, alpha, alpha_c, eps;              // damp_c = 1 - dampening, alpha_c = 1 - alpha
+    float ema_decay, ema_c;
+    int nesterov, first, ema_mode;                                // first: SGD's first step with momentum: buf = g' (buf is not read)
+    const float* clip;                                            // rule_ema_kernel<.., .., true>: {norm, coef, ok, 0}
+    int skip_nonfinite;
+};
+
+template <int RULE, bool MOM>
+__device__ __forceinline__ void rule_one(const RuleArgs& a, float& p, float g, float& buf, float& sq) {
+    if (a.wd != 0.f) g = fmaf(a.wd, p, g);
+    if (RULE == RULE_SGD) {
+        if (MOM) {
+            buf = a.first ? g : fmaf(a.damp_c, g, a.mom * buf);
+            g = a.nesterov ? fmaf(a.mom, buf, g) : buf;
+        }
+        p = fmaf(-a.lr, g, p);
+    } else {
+        sq = sq * a.alpha + a.alpha_c * g * g;
+        const float avg = sqrtf(sq) + a.eps;
+        if (MOM) {
+            buf = a.mom * buf + g / avg;
+            p = fmaf(-a.lr, buf, p);
+        } else {
+            p = p - a.lr * (g / avg);
+        }
+    }
+}
+
+// adam_ema_kernel's mapping and access widths; MOM: the rule reads / writes the momentum buffer, RULE_RMSPROP: square_avg.  A chunk
+// whose gradient, or a state tensor the rule needs, is NULL gets no update (its EMA part still runs).
+template <int RULE, bool MOM, bool CLIP>
+__global__ void __launch_bounds__(256) rule_ema_kernel(const RuleArgs a) {
+    constexpr bool SQ = RULE == RULE_RMSPROP;
+    const BbdmOptChunk c = a.table[blockIdx.x];
+    float* __restrict__ p = c.param;
+    const float* __restrict__ g = c.grad;
+    float* __restrict__ m = c.exp_avg;
+    float* __restrict__ v = c.exp_avg_sq;
+    float* __restrict__ s = c.shadow;
+    const int n = c.n;
+    bool upd = g != nullptr && (!MOM || m != nullptr) && (!SQ || v != nullptr);
+    float coef = 1.f;
+    if (CLIP) {
+        coef = a.clip[1];
+        if (a.skip_nonfinite && a.clip[2] == 0.f) upd = false;       // non-finite norm: p and the state stay as they are
+    }
+    const bool ema = a.ema_mode != 0 && s != nullptr;
+    const bool rd_m = MOM && !(RULE == RULE_SGD && a.first);
+    uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)s;
+    if (MOM) al |= (uintptr_t)m;
+    if (SQ) al |= (uintptr_t)v;
+    if ((al & 15) == 0) {
+        const int n4 = n >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            float4 pv = reinterpret_cast<const float4*>(p)[i];
+            if (upd) {
+                float4 gv = reinterpret_cast<const float4*>(g)[i];
+                if (CLIP) { gv.x *= coef; gv.y *= coef; gv.z *= coef; gv.w *= coef; }
+                float4 mv = make_float4(0.f, 0.f, 0.f, 0.f), vv = mv;
+                if (rd_m) mv = reinterpret_cast<const float4*>(m)[i];
+                if (SQ) vv = reinterpret_cast<const float4*>(v)[i];
+                rule_one<RULE, MOM>(a, pv.x, gv.x, mv.x, vv.x);
+                rule_one<RULE, MOM>(a, pv.y, gv.y, mv.y, vv.y);
+                rule_one<RULE, MOM>(a, pv.z, gv.z, mv.z, vv.z);
+                rule_one<RULE, MOM>(a, pv.w, gv.w, mv.w, vv.w);
+                if (MOM) reinterpret_cast<float4*>(m)[i] = mv;
+                if (SQ) reinterpret_cast<float4*>(v)[i] = vv;
+                reinterpret_cast<float4*>(p)[i] = pv;
+            }
+            if (ema) {
+                float4 sv = pv;
+                if (a.ema_mode == 1) {
+                    const float4 o = reinterpret_cast<const float4*>(s)[i];
+                    sv.x = a.ema_c * pv.x + a.ema_decay * o.x;
+                    sv.y = a.ema_c * pv.y + a.ema_decay * o.y;
+                    sv.z = a.ema_c * pv.z + a.ema_decay * o.z;
+                    sv.w = a.ema_c * pv.w + a.ema_decay * o.w;
+                }
+                reinterpret_cast<float4*>(s)[i] = sv;
+            }
+        }
+    }
+    // element accesses: the tail of an aligned chunk, or all of an unaligned one
+    for (int i = ((al & 15) == 0 ? (n >> 2) << 2 : 0) + threadIdx.x; i < n; i += 256) {
+        float pv = p[i];
+        if (upd) {
+            float mv = rd_m ? m[i] : 0.f, vv = SQ ? v[i] : 0.f;
+            rule_one<RULE, MOM>(a, pv, CLIP ? g[i] * coef : g[i], mv, vv);
+            if (MOM) m[i] = mv;
+            if (SQ) v[i] = vv;
+            p[i] = pv;
+        }
+        if (ema) s[i] = a.ema_mode == 1 ? a.ema_c * pv + a.ema_decay * s[i] : pv;
     }
 }
 
@@ -277,6 +387,97 @@ extern "C" int bbdm_adam_ema_step_clip_f32(const BbdmOptChunk* table, int nchunk
     BBDM_REQUIRE(clip != nullptr, "adam_ema_clip: clip (the finalize's output) is NULL");
     return adam_ema_launch(table, nchunks, do_adam, lr, beta1, beta2, eps, weight_decay, step, ema_mode, ema_decay, clip,
                            skip_nonfinite != 0, stream);
+}
+
+template <int RULE>
+static void rule_ema_dispatch(const RuleArgs& a, int nchunks, void* stream) {
+    const dim3 grid((unsigned)nchunks), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (a.mom != 0.f) {
+        if (a.clip != nullptr) hipLaunchKernelGGL((rule_ema_kernel<RULE, true, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((rule_ema_kernel<RULE, true, false>), grid, block, 0, st, a);
+    } else {
+        if (a.clip != nullptr) hipLaunchKernelGGL((rule_ema_kernel<RULE, false, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((rule_ema_kernel<RULE, false, false>), grid, block, 0, st, a);
+    }
+}
+
+// hyper-parameters arrive as Python doubles and are rounded to fp32 once, after any host arithmetic (1 - dampening, 1 - alpha), as in
+// adam_ema_launch
+static int rule_ema_common(RuleArgs& a, const BbdmOptChunk* table, int nchunks, double lr, double weight_decay, double momentum,
+                           int ema_mode, double ema_decay, const float* clip, int skip_nonfinite, const char* what) {
+    BBDM_REQUIRE(table && nchunks > 0, "%s: empty chunk table", what);
+    BBDM_REQUIRE(ema_mode >= 0 && ema_mode <= 2, "%s: ema_mode=%d (0 none, 1 decay, 2 copy)", what, ema_mode);
+    BBDM_REQUIRE(lr >= 0. && weight_decay >= 0. && momentum >= 0., "%s: bad hyper-parameters (lr=%g weight_decay=%g momentum=%g)", what,
+                 lr, weight_decay, momentum);
+    a.table = table;
+    a.lr = (float)lr;
+    a.wd = (float)weight_decay;
+    a.mom = (float)momentum;
+    a.damp_c = 1.f; a.alpha = 0.f; a.alpha_c = 1.f; a.eps = 0.f;
+    a.nesterov = 0; a.first = 0;
+    a.ema_decay = (float)ema_decay;
+    a.ema_c = (float)(1.0 - ema_decay);
+    a.ema_mode = ema_mode;
+    a.clip = clip;
+    a.skip_nonfinite = skip_nonfinite;
+    return BBDM_OK;
+}
+
+static int sgd_ema_launch(const BbdmOptChunk* table, int nchunks, double lr, double momentum, double dampening, double weight_decay,
+                          int nesterov, int first, int ema_mode, double ema_decay, const float* clip, int skip_nonfinite, void* stream) {
+    RuleArgs a;
+    const int rc = rule_ema_common(a, table, nchunks, lr, weight_decay, momentum, ema_mode, ema_decay, clip, skip_nonfinite, "sgd_ema");
+    if (rc != BBDM_OK) return rc;
+    BBDM_REQUIRE(!nesterov || (momentum > 0. && dampening == 0.), "sgd_ema: nesterov needs momentum > 0 and dampening == 0 (momentum=%g "
+                 "dampening=%g)", momentum, dampening);
+    a.damp_c = (float)(1.0 - dampening);
+    a.nesterov = nesterov != 0;
+    a.first = first != 0;
+    rule_ema_dispatch<RULE_SGD>(a, nchunks, stream);
+    BBDM_CHECK_LAUNCH("sgd_ema");
+    return BBDM_OK;
+}
+
+static int rmsprop_ema_launch(const BbdmOptChunk* table, int nchunks, double lr, double alpha, double eps, double weight_decay,
+                              double momentum, int ema_mode, double ema_decay, const float* clip, int skip_nonfinite, void* stream) {
+    RuleArgs a;
+    const int rc = rule_ema_common(a, table, nchunks, lr, weight_decay, momentum, ema_mode, ema_decay, clip, skip_nonfinite,
+                                   "rmsprop_ema");
+    if (rc != BBDM_OK) return rc;
+    BBDM_REQUIRE(alpha >= 0. && eps >= 0., "rmsprop_ema: bad hyper-parameters (alpha=%g eps=%g)", alpha, eps);
+    a.alpha = (float)alpha;
+    a.alpha_c = (float)(1.0 - alpha);
+    a.eps = (float)eps;
+    rule_ema_dispatch<RULE_RMSPROP>(a, nchunks, stream);
+    BBDM_CHECK_LAUNCH("rmsprop_ema");
+    return BBDM_OK;
+}
+
+extern "C" int bbdm_sgd_ema_step_f32(const BbdmOptChunk* table, int nchunks, double lr, double momentum, double dampening,
+                                     double weight_decay, int nesterov, int first, int ema_mode, double ema_decay, void* stream) {
+    return sgd_ema_launch(table, nchunks, lr, momentum, dampening, weight_decay, nesterov, first, ema_mode, ema_decay, nullptr, 0, stream);
+}
+
+extern "C" int bbdm_sgd_ema_step_clip_f32(const BbdmOptChunk* table, int nchunks, double lr, double momentum, double dampening,
+                                          double weight_decay, int nesterov, int first, int ema_mode, double ema_decay,
+                                          const float* clip, int skip_nonfinite, void* stream) {
+    BBDM_REQUIRE(clip != nullptr, "sgd_ema_clip: clip (the finalize's output) is NULL");
+    return sgd_ema_launch(table, nchunks, lr, momentum, dampening, weight_decay, nesterov, first, ema_mode, ema_decay, clip,
+                          skip_nonfinite != 0, stream);
+}
+
+extern "C" int bbdm_rmsprop_ema_step_f32(const BbdmOptChunk* table, int nchunks, double lr, double alpha, double eps,
+                                         double weight_decay, double momentum, int ema_mode, double ema_decay, void* stream) {
+    return rmsprop_ema_launch(table, nchunks, lr, alpha, eps, weight_decay, momentum, ema_mode, ema_decay, nullptr, 0, stream);
+}
+
+extern "C" int bbdm_rmsprop_ema_step_clip_f32(const BbdmOptChunk* table, int nchunks, double lr, double alpha, double eps,
+                                              double weight_decay, double momentum, int ema_mode, double ema_decay, const float* clip,
+                                              int skip_nonfinite, void* stream) {
+    BBDM_REQUIRE(clip != nullptr, "rmsprop_ema_clip: clip (the finalize's output) is NULL");
+    return rmsprop_ema_launch(table, nchunks, lr, alpha, eps, weight_decay, momentum, ema_mode, ema_decay, clip, skip_nonfinite != 0,
+                              stream);
 }
 
 extern "C" size_t bbdm_grad_norm_cells_bytes(void) { return (size_t)NORM_CELLS * NORM_CELL_WORDS * sizeof(unsigned long long); }

@@ -710,6 +710,32 @@ int bbdm_adam_ema_step_clip_f32(const BbdmOptChunk* table, int nchunks, int do_a
                                 const float* clip, int skip_nonfinite, void* stream);
 int bbdm_grad_scale_f32(const BbdmOptChunk* table, int nchunks, const float* clip, void* stream);
 
+/* ---- the other two optimizers of the training config (ABI 30) ---------------------------------------------------------- */
+/* Replace torch.optim.SGD(parameters, lr, momentum=0.9).step() (runners/utils.py:54-55) and torch.optim.RMSprop(parameters, lr,
+ * weight_decay).step() (runners/utils.py:52-53), both called at runners/BaseRunner.py:413-415, plus EMA.update()
+ * (runners/base/EMA.py:21-29), with ONE launch over the same BbdmOptChunk table: the `exp_avg` slot carries the momentum buffer (NULL
+ * when momentum == 0), the `exp_avg_sq` slot RMSprop's square_avg (NULL for SGD).  A chunk whose grad, or a state pointer the rule
+ * needs, is NULL gets no update; its EMA part (ema_mode / ema_decay as in bbdm_adam_ema_step_f32, on the UPDATED p) still runs.
+ * Arithmetic: torch's single-tensor formulas in fp32, no FMA contraction (an add with a scalar alpha is one rounding, as in ATen):
+ *   SGD      g' = g + weight_decay * p;  momentum != 0: buf = first ? g' : momentum * buf + (1 - dampening) * g',
+ *            g' = nesterov ? g' + momentum * buf : buf;  p = p - lr * g'.  `first` != 0: the step that creates the momentum buffer
+ *            (torch: buf = clone(grad)); the buffer is written, not read.  nesterov needs momentum > 0 and dampening == 0;
+ *   RMSprop  g' = g + weight_decay * p;  sq = alpha * sq + (1 - alpha) * g' * g';  avg = sqrt(sq) + eps;
+ *            momentum != 0: buf = momentum * buf + g' / avg, p = p - lr * buf;  else p = p - lr * (g' / avg)   (not centered).
+ * The _clip forms take `clip` = the output of bbdm_grad_norm_finalize_f32 and use g * coef (one fp32 rounding) in place of g; with
+ * skip_nonfinite != 0 and ok == 0 the parameter and the state stay untouched and the EMA part still runs, as in
+ * bbdm_adam_ema_step_clip_f32.  coef == 1: the bits of the plain form. */
+int bbdm_sgd_ema_step_f32(const BbdmOptChunk* table, int nchunks, double lr, double momentum, double dampening, double weight_decay,
+                          int nesterov, int first, int ema_mode, double ema_decay, void* stream);
+int bbdm_sgd_ema_step_clip_f32(const BbdmOptChunk* table, int nchunks, double lr, double momentum, double dampening,
+                               double weight_decay, int nesterov, int first, int ema_mode, double ema_decay, const float* clip,
+                               int skip_nonfinite, void* stream);
+int bbdm_rmsprop_ema_step_f32(const BbdmOptChunk* table, int nchunks, double lr, double alpha, double eps, double weight_decay,
+                              double momentum, int ema_mode, double ema_decay, void* stream);
+int bbdm_rmsprop_ema_step_clip_f32(const BbdmOptChunk* table, int nchunks, double lr, double alpha, double eps, double weight_decay,
+                                   double momentum, int ema_mode, double ema_decay, const float* clip, int skip_nonfinite,
+                                   void* stream);
+
 /* ---- sample egress ------------------------------------------------------------------------ */
 /* fp32 NCHW [N,C,H,W] -> uint8 NHWC [N,H,W,C] with the arithmetic of save_single_image (runners/utils.py:67-74):
  * to_normal != 0: v = clamp(v * 0.5 + 0.5, 0, 1); then u8 = (uint8) clamp(v * 255 + 0.5, 0, 255) (truncation) -- each
