@@ -15,7 +15,7 @@ There is no PyTorch fallback: without the HIP library, or on a non-GPU tensor, `
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -289,23 +289,45 @@ class _GnPre(tuple):
     tail: tuple = ()
     h2 = None          # reference of the device float that bounds the producer's output (see _Pre), or None
 
-    def __new__(cls, head, tail, h2=None):
+    def __new__(cls, head, tail, h2=None, choice=None):
         o = super().__new__(cls, head)
         o.tail = tuple(tail)
-        o.h2 = h2
+        o.h2, o.choice = h2, choice
         return o
 
 
 class _Pre(tuple):
     """(pre_scale, pre_bias, pre_ld, pre_silu) of a fused producer -- all None / 0 when the tensor was materialised -- plus ``h2``: the
     reference of a device float >= max |value| of what the consumer convolves (a GroupNorm output is bounded by its coefficients alone:
-    csrc/groupnorm.hip, h2_gn_bounds_kernel), which lets the consumer's tile GEMMs run on the fp16-pair planes (csrc/h2_split.h)."""
+    csrc/groupnorm.hip, h2_gn_bounds_kernel), which lets the consumer's tile GEMMs run on the fp16-pair planes (csrc/h2_split.h);
+    and ``choice``: the kernel form of the consumer, where the emitter of its input had to know it (_Plan._conv_choice)."""
     h2 = None
 
-    def __new__(cls, head, h2=None):
+    def __new__(cls, head, h2=None, choice=None):
         o = super().__new__(cls, head)
-        o.h2 = h2
+        o.h2, o.choice = h2, choice
         return o
+
+
+class _ConvChoice(NamedTuple):
+    """The kernel form of one conv layer's forward, decided once (_Plan._conv_choice)."""
+    kind: str                   # "phases" (conv3x3(nearest x2 (x)) as four phase filters on x), "winograd", "1x1" (matrix core) or "direct"
+    m: int = 0                  # Winograd tile
+    H: int = 0                  # the tile GEMMs' grid (x's own for the phase filters) ...
+    W: int = 0
+    cout: int = 0               # ... and their output channels (4 Cout for the phase filters)
+    bf3: object = False         # plane mode of the tile GEMMs (_Plan._use_bf3)
+    keeps_V: bool = False       # the training forward keeps the transformed input for the Winograd-domain weight gradient
+    form: Optional[tuple] = None    # "1x1": (entry point, plane layout of the weights, does it take the input's bound)
+    folds_gn: bool = False      # the input transform can form the coefficients of a GroupNorm producer itself
+
+
+class _SavedV(NamedTuple):
+    """The transformed input a training forward kept for the Winograd-domain weight gradient of its layer."""
+    v: object                   # fp32 V (a view), or -- ``transposed`` -- the reference of the transposed planes
+    m: int                      # Winograd tile
+    transposed: bool = False
+    bound: object = None        # the transposed planes are fp16 pairs under this bound slot (None: the exact bf16 split)
 
 
 def _round4(c):
@@ -755,7 +777,7 @@ class _Plan:
         self._h2_table = None
         self._h2_dy_slots = 0                        # training: bound slots of gradient tensors (the tail of _h2_bounds, _dy_bound)
         self._h2_x_slots = 0                         # bound slots of raw block inputs (_stats_bound)
-        self._saved_V: Dict[int, tuple] = {}         # training: id(conv weight) -> (V kept by the forward, tile m)
+        self._saved_V: Dict[int, _SavedV] = {}       # training: id(conv weight) -> the V kept by the forward
         self._fused_train = set()                    # training: id(conv weight) of layers whose GN->SiLU input was never materialised
         self.film, self.film_total, self.resblocks, self._film_key, self.film_wp = None, 0, [], None, None
         # (id(buffer), channel offset) -> record of the conv op that LAST wrote that channel slice: where a GroupNorm
@@ -993,9 +1015,13 @@ class _Plan:
             self._op("bbdm_groupnorm_apply_f32", x, x.ld, ref, self._pref(gn.weight), self._pref(gn.bias),
                      film, self.film_total, y, y.ld, N, x.H, x.W, x.C, self.GROUPS, float(gn.eps), silu, resample)
         else:
-            self._op("bbdm_groupnorm_apply_f32", x, x.ld, None, None, None, None, 0, y, y.ld, N, x.H, x.W,
-                     x.C, 1, 0.0, 0, resample)
+            self._resample(x, y, resample)
         return y
+
+    def _resample(self, x: _View, y: _View, mode: int):
+        """y = x copied (0), 2x2-average-pooled (1), nearest-upsampled x2 (2) or thinned to every 2nd pixel (3): the GroupNorm apply pass
+        without a GroupNorm."""
+        self._op("bbdm_groupnorm_apply_f32", x, x.ld, None, None, None, None, 0, y, y.ld, self.N, x.H, x.W, x.C, 1, 0.0, 0, mode)
 
     NO_PRE = (None, None, 0, 0)
 
@@ -1060,18 +1086,6 @@ class _Plan:
         self._bop("bbdm_absmax_rows_f32", dy, dy.ld, self.N * dy.H * dy.W, dy.C, ref)
         return ref
 
-    def _conv1x1_h2_ok(self, pixels: int, cin: int, cout: int) -> bool:
-        """Would a 1x1 convolution of this size with a bounded input run on bbdm_conv1x1_h2q_f32?  (inference, wide layers: the small
-        problems keep the small-problem kernel)"""
-        return bool(getattr(self.m, "conv1x1_h2", True) and self._h2_on(1) and cin % 16 == 0 and cout % 4 == 0
-                    and (pixels // 256) * -(-cout // 128) >= self.m.bf3_min_tiles)
-
-    def _conv1x1_h2s_ok(self, pixels: int, cin: int, cout: int) -> bool:
-        """... or, below that size, on the small-problem form bbdm_conv1x1_h2s_f32 (bound by its weight stream: a third fewer bytes)?"""
-        return bool(not self.training and getattr(self.m, "conv1x1_h2", True) and self._h2_on(1) and self.m.conv1x1_small
-                    and not self._conv1x1_h2_ok(pixels, cin, cout) and cin % 64 == 0 and cout % 4 == 0
-                    and not (self.lib.bbdm_gemm_bf3_supported(pixels, cin, cout) and (pixels // 256) * -(-cout // 128) >= self.m.bf3_min_tiles))
-
     def _stats_bound(self, slot: int):
         """Bound slot for the RAW tensor whose GroupNorm statistics are accumulator ``slot``: the largest root-sum-of-squares over its
         (image, group) cells (csrc/groupnorm.hip: h2_stats_bound_kernel).  Emitted where the statistics are complete."""
@@ -1101,17 +1115,19 @@ class _Plan:
         into the direct conv kernel only for the narrow head (``fuse_direct``; elsewhere it costs more MFMA stalls than the pass it
         removes) but always into the HBM-bound Winograd input transform of ``consumer``, where it is
         free."""
-        up = 2 if upsample else 1         # (``upsample``: the consumer convolves the nearest x2 upsampling of the activated tensor)
-        fuse = fuse_direct or (consumer is not None and self.m.winograd_fuse_groupnorm
-                                                        and self._winograd_ok(consumer, up * x.H, up * x.W, x.C))
+        # (``upsample``: the consumer convolves the nearest x2 upsampling of the activated tensor)
+        choice = None if consumer is None else self._conv_choice(consumer, x, upsample=upsample, bounded=self._h2_on(1) and gn is not None)
+        wino = choice is not None and choice.kind in ("phases", "winograd")
+        fuse = fuse_direct or (wino and self.m.winograd_fuse_groupnorm)
         assert not upsample or (fuse and not self.training)
         if self.training:
             # Training plans materialise the activated tensor for the weight gradient -- unless that gradient will contract the V
-            # this layer's forward keeps (Winograd layer, same tile both ways: _emit_winograd / conv_bwd): then nothing
+            # this layer's forward keeps (Winograd layer, same tile both ways: _emit_winograd / _emit_wgrad): then nothing
             # re-reads the activation and GN -> FiLM -> SiLU folds into the input transform exactly as in sampling.
-            if not (self.m.winograd_fuse_groupnorm and self._train_keeps_V(consumer, x)):
-                bref = self._gn_bound(x, gn, film_off) if (consumer is not None and self._winograd_ok(consumer, x.H, x.W, x.C)) else None
-                return self._gn_apply(x, gn, film_off, silu=silu, resample=0, name=name), _Pre(self.NO_PRE, h2=bref)
+            if not (self.m.winograd_fuse_groupnorm and wino and choice.keeps_V):
+                bref = self._gn_bound(x, gn, film_off) if wino else None
+                return (self._gn_apply(x, gn, film_off, silu=silu, resample=0, name=name),
+                        _Pre(self.NO_PRE, h2=bref, choice=choice if wino else None))
             self._fused_train.add(id(consumer.weight))
         elif not fuse:
             return self._gn_apply(x, gn, film_off, silu=silu, resample=0, name=name), self.NO_PRE
@@ -1121,10 +1137,10 @@ class _Plan:
         self._gn_count += 1
         self._emit_stats(x, ref)
         film = None if film_off is None else _TensorRef(self.film, 4 * film_off)
-        if self._gn_folds_into_transform(consumer, x, up, h2=bref is not None):
+        if choice is not None and choice.folds_gn:
             # small problem: the consumer's input transform forms the coefficients from the statistics (one launch fewer)
             return x, _GnPre((ref, None, x.C, silu), (self._pref(gn.weight), self._pref(gn.bias), film, self.film_total,
-                                                       x.H * x.W, self.GROUPS, float(gn.eps)), h2=bref)
+                                                       x.H * x.W, self.GROUPS, float(gn.eps)), h2=bref, choice=choice)
         k = self._n_coeffs
         self._n_coeffs += 1
         self._coeff_need = max(self._coeff_need, N * x.C)
@@ -1135,39 +1151,7 @@ class _Plan:
         # every size: profiles/r04_stats_tail_negative.md.)
         self._op("bbdm_groupnorm_coeffs_f32", ref, self._pref(gn.weight), self._pref(gn.bias), film, self.film_total, sc, bi,
                  x.C, N, x.H * x.W, x.C, self.GROUPS, float(gn.eps))
-        return x, _Pre((sc, bi, x.C, silu), h2=bref)
-
-    def _gn_folds_into_transform(self, consumer, x: _View, up: int, h2: bool = False) -> bool:
-        """Will ``consumer`` (a 3x3 conv on GN(x), nearest-upsampled ``up`` x) run as a Winograd layer on the pre-split planes, small
-        enough for its input transform to form the GroupNorm coefficients itself?  Mirrors the choices of :meth:`_emit_conv`."""
-        m = self.m
-        if self.training or consumer is None or not m.gn_in_transform or not (m.gemm_bf3 and m.gemm_bf3p):
-            return False
-        H, W, cout = up * x.H, up * x.W, consumer.weight.shape[0]
-        wm = self._winograd_ok(consumer, H, W, x.C)
-        if not wm or wm == 8 or x.C % 16 or (x.C // self.GROUPS) % 2 or consumer.weight.shape[1] != x.C:
-            return False                      # (m = 8: large layers only, no coefficient-folding input transform)
-        small = self._wino_small()
-        cands = [(wm, H, W, cout)]
-        if up == 2 and m.upsample_phases:         # conv3x3(nearest x2 (x)) may run as four phase filters on x itself
-            wl = phase_filter_tile(self.N, x.H, x.W, x.C, 4 * cout, m.winograd, small, m.upsample_f72 and not self.training)
-            if wl >= min(wm, 6):
-                if wl == 7:
-                    return False                  # (F(7x7, 2x2): large layers only, no coefficient-folding input transform)
-                cands = [(wl, x.H, x.W, 4 * cout)]
-        for w_, h_, ww_, co_ in cands:
-            if self._use_bf3(w_, h_, ww_, x.C, co_, h2=h2) not in ("p", "h") or \
-                    self.lib.bbdm_winograd_tiles(w_, self.N, h_, ww_) > m.gn_in_transform:
-                return False
-        return True
-
-    def _train_keeps_V(self, consumer, x: _View) -> bool:
-        """Will the training forward of conv ``consumer`` on ``x`` keep its transformed input for the weight gradient?"""
-        if consumer is None or not self.m.winograd_wgrad:
-            return False
-        w = consumer.weight
-        wm = self._winograd_ok(consumer, x.H, x.W, x.C)
-        return bool(wm) and w.shape[1] == x.C and self._wgrad_tile(x.H, x.W, x.C, w.shape[0]) == wm
+        return x, _Pre((sc, bi, x.C, silu), h2=bref, choice=choice)
 
     def _winograd_ok(self, mod, H, W, cin_pad, flags=0) -> int:
         """Winograd output tile for this conv (0 = direct kernel)."""
@@ -1219,14 +1203,51 @@ class _Plan:
             return "p"          # (keeps_V: the weight gradient then contracts the TRANSPOSED planes the input transform also writes)
         return bool(self.lib.bbdm_gemm_bf3_supported(tiles, cin_pad, cout))
 
-    def _keeps_V(self, wm, H, W, cin_pad, cin, cout, upsample, bwd) -> bool:
-        """Training forward: does this Winograd layer keep its fp32 V for the Winograd-domain weight gradient?"""
-        return bool(self.training and not bwd and not upsample and cin_pad == cin and self.m.winograd_wgrad
-                    and self._wgrad_tile(H, W, cin_pad, cout) == wm)
+    def _conv_choice(self, mod, x: _View, *, upsample: bool = False, flags: int = 0, has_residual: bool = False, bounded: bool = False,
+                     plain_input: bool = True) -> _ConvChoice:
+        """The kernel form of conv / Linear ``mod`` on ``x`` (``upsample``: on its nearest x2 upsampling), with ``flags`` / a residual in its
+        epilogue.  ``bounded``: its input comes with a bound slot; ``plain_input``: without a fused producer.  Pure: emits, allocates and
+        packs nothing -- _emit_conv acts on it, and so does whoever has to know the form before the layer is emitted."""
+        m, lib = self.m, self.lib
+        w = mod.weight
+        cout = w.shape[0]
+        H, W = (2 * x.H, 2 * x.W) if upsample else (x.H, x.W)
+        h2 = bounded and self._h2_on(1)
+        wm = self._winograd_ok(mod, H, W, x.C, flags)
+        # the input transform forms the coefficients of a GroupNorm producer itself (bbdm_winograd_input_bf3p_gn_f32) on the pre-split
+        # planes of inference plans, up to UNetModel.gn_in_transform tiles; m = 8 at the convolved size and F(7x7, 2x2) are large layers
+        # only and have no such transform
+        gn_ok = bool(not self.training and m.gn_in_transform and m.gemm_bf3 and m.gemm_bf3p and wm != 8 and x.C % 16 == 0
+                     and (x.C // self.GROUPS) % 2 == 0 and w.shape[1] == x.C)
 
-    def _emit_winograd(self, x, cin_pad, pw, pre, upsample, H, W, residual, res_ld, dest, flags, bwd=False):
+        def wino(kind, wl, h, ww, co, keeps=False, gn=gn_ok):
+            mode = self._use_bf3(wl, h, ww, x.C, co, keeps_V=keeps, h2=h2)
+            return _ConvChoice(kind, wl, h, ww, co, mode, keeps, None,
+                               gn and mode in ("p", "h") and lib.bbdm_winograd_tiles(wl, self.N, h, ww) <= m.gn_in_transform)
+        if wm and upsample and m.upsample_phases and not has_residual and flags == 0 and w.shape[1] == x.C:
+            # conv3x3(nearest x2 (x)) = four phase filters on x (Cin -> 4 Cout): same GEMM work, the input transform and the GEMM's
+            # A operand shrink 4x -- taken where x's own tile grid earns the same Winograd tile as the upsampled one
+            wl = f72 = phase_filter_tile(self.N, x.H, x.W, x.C, 4 * cout, m.winograd, self._wino_small(), m.upsample_f72 and not self.training)
+            if wl == 7 and self._use_bf3(7, x.H, x.W, x.C, 4 * cout, h2=h2) not in ("p", "h"):
+                wl = 6                            # (F(7x7, 2x2) exists on the pre-split planes only)
+            if wl >= min(wm, 6):               # (m = 8 at the upsampled size does not beat the phase filters' 4x smaller input transform)
+                return wino("phases", wl, x.H, x.W, 4 * cout, gn=gn_ok and f72 != 7)
+        if wm:
+            # training: the Winograd-domain weight gradient contracts the SAME transformed input where it takes the same tile -- the
+            # forward then keeps V (_emit_winograd) and nothing re-reads the layer's input
+            keeps = bool(self.training and not upsample and w.shape[1] == x.C and m.winograd_wgrad
+                         and self._wgrad_tile(H, W, x.C, cout) == wm)
+            return wino("winograd", wm, H, W, cout, keeps)
+        if (w.shape[2] if w.dim() == 4 else 1) == 1 and plain_input and flags == 0:
+            form = self._conv1x1_form(self.N * x.H * x.W, x.C, cout, bounded)
+            if form is not None:
+                return _ConvChoice("1x1", form=form)
+        return _ConvChoice("direct")
+
+    def _emit_winograd(self, x, cin_pad, pw, pre, upsample, H, W, residual, res_ld, dest, flags, bwd=False, keeps=False):
         """input transform -> 16 batched GEMMs -> output transform (csrc/winograd.hip).  ``pw.phases``: H, W are x's; the GEMMs produce the
-        4 Cout phase channels and the output transform scatters them over the [2H, 2W] result (BBDM_CONV_OUT_PHASES)."""
+        4 Cout phase channels and the output transform scatters them over the [2H, 2W] result (BBDM_CONV_OUT_PHASES).  ``keeps``: the
+        training forward keeps the transformed input for the layer's weight gradient (_ConvChoice.keeps_V)."""
         emit = self._bop if bwd else self._op
         N, cout_y, wm = self.N, dest.C, pw.m
         cout = 4 * cout_y if pw.phases else cout_y          # channels of M
@@ -1244,7 +1265,6 @@ class _Plan:
         ksplit = int(self.lib.bbdm_winograd_gemm_bf3p_splits(wm, N, H, W, cin_pad, cout)) if (split and not pw.phases) else 1
         self._wino_m_need = max(self._wino_m_need, ksplit * wino_planes(wm) * tiles * cout)
         vbuf = self._wino_v
-        keeps = self._keeps_V(wm, H, W, cin_pad, pw.cin, cout, upsample, bwd)
         if keeps and not split:
             # training: this layer's weight gradient contracts the SAME transformed input (csrc/winograd_wgrad.hip) -- keep V
             # in a buffer of its own instead of re-running the input transform in the backward pass (memory: (m+2)^2/m^2 x
@@ -1252,14 +1272,14 @@ class _Plan:
             b = _Buf(wino_planes(wm) * tiles * cin_pad)
             self.bufs.append(b)
             vbuf = _View(b, 0, cin_pad, 1, 1, 1, cin_pad)
-            self._saved_V[id(pw.weight)] = (vbuf, wm)
+            self._saved_V[id(pw.weight)] = _SavedV(vbuf, wm)
         if keeps and split:
             # ... as bf16 planes: the forward GEMM reads the shared scratch copy, the weight gradient the TRANSPOSED copy (rows =
             # channels, contraction index = tiles) that the same input-transform launch writes -- 6 B per element kept
             vt_h2 = h2 and self._h2_on(3)         # the weight gradient's TN GEMM on the fp16 pair as well: the transposed copy likewise
             nbytes = (self.lib.bbdm_gemm_h2p_tn_at_bytes if vt_h2 else self.lib.bbdm_gemm_bf3p_tn_at_bytes)(wino_planes(wm), tiles, cin_pad)
             vt = _TensorRef(torch.empty(nbytes, dtype=torch.uint8, device=self.device))
-            self._saved_V[id(pw.weight)] = (vt, wm, "tr", pre.h2) if vt_h2 else (vt, wm, "tr")
+            self._saved_V[id(pw.weight)] = _SavedV(vt, wm, True, pre.h2 if vt_h2 else None)
             emit(_OpName("bbdm_winograd_input_f32", "bbdm_winograd_input_h2p_tr2_f32" if vt_h2 else
                          "bbdm_winograd_input_h2p_tr_f32" if h2 else "bbdm_winograd_input_bf3p_tr_f32"),
                  wm, x, x.ld, vbuf, *(pre or self.NO_PRE), 0, N, H, W, cin_pad, vt, *vb)
@@ -1292,15 +1312,19 @@ class _Plan:
                        N, H, W, cout_y, None, 0, 0, None, 0, 0, *ks_tail)
             self._note_writer(dest, rec, 12)
 
-    def _conv1x1_form(self, pixels: int, cin: int, cout: int, bounded: bool):
+    def _conv1x1_form(self, pixels: int, cin: int, cout: int, bounded: bool, dy_ld: Optional[int] = None):
         """The matrix-core form of a plain 1x1 convolution / Linear (no fused producer, no flags; ``bounded``: its input carries a bound):
         (entry point, plane layout of its weights, does it take the bound), or None = the direct kernel.  The order of the tests is
-        the policy."""
+        the policy.  ``dy_ld``: the layer is a DATA GRADIENT dX = dY W (``cin`` = channels, ``dy_ld`` = pitch of dY, whose measured maximum
+        is its bound) -- the fp16 pair from UNetModel.gemm_h2_train = 2, and the wide forms only."""
         m = self.m
-        if bounded and self._conv1x1_h2_ok(pixels, cin, cout):
+        dgrad = dy_ld is not None
+        wide = (pixels // 256) * -(-cout // 128) >= m.bf3_min_tiles
+        h2 = bool(bounded and getattr(m, "conv1x1_h2", True) and self._h2_on(2 if dgrad else 1))
+        if h2 and wide and cin % 16 == 0 and cout % 4 == 0 and (not dgrad or dy_ld % 4 == 0):
             # wide layer whose input carries a bound: the fp16-pair planes (csrc/gemm_bf3p.hip: gemm_bf3q_pipe_kernel<NP = 2>)
             return "bbdm_conv1x1_h2q_f32", "h", True
-        if m.gemm_bf3 and self.lib.bbdm_gemm_bf3_supported(pixels, cin, cout) and (pixels // 256) * -(-cout // 128) >= m.bf3_min_tiles:
+        if m.gemm_bf3 and self.lib.bbdm_gemm_bf3_supported(pixels, cin, cout) and wide:
             # wide 1x1 convolutions / Linears (skip connections, qkv / proj_out, transformer projections): the fp32-accurate
             # bf16x3 GEMM with bias + residual in its epilogue (csrc/gemm_bf3.hip); small problems keep the split-K f32 kernel
             # ... on the pipelined kernel (csrc/gemm_bf3p.hip: gemm_bf3q_pipe_kernel, 200 - 214 instead of 165 - 192 TFLOP/s) where
@@ -1308,7 +1332,10 @@ class _Plan:
             if (-(-cout // 128) * 128) % 256 == 0:
                 return "bbdm_conv1x1_bf3q_f32", "p", False
             return "bbdm_conv1x1_bf3_f32", True, False
-        if bounded and self._conv1x1_h2s_ok(pixels, cin, cout):
+        if dgrad:
+            return None
+        if h2 and not self.training and m.conv1x1_small and cin % 64 == 0 and cout % 4 == 0:
+            # ... below that size, inference: its small-problem form (bound by its weight stream: a third fewer bytes)
             return "bbdm_conv1x1_h2s_f32", "h", True
         if m.gemm_bf3 and m.conv1x1_small and cin % 64 == 0 and cout % 4 == 0:
             # small 1x1 convolutions / Linears: bound by the length of a workgroup's chain of K steps, not by the matrix pipe -- the
@@ -1333,40 +1360,25 @@ class _Plan:
         if res_ld is None:
             assert residual is None or residual.C == cout
             res_ld = residual.ld if residual is not None else 0
-        H, W = (2 * x.H, 2 * x.W) if upsample else (x.H, x.W)
-        h2 = getattr(pre, "h2", None) is not None and self._h2_on(1)
-        wm = self._winograd_ok(mod, H, W, x.C, flags)
-        if wm and upsample and self.m.upsample_phases and residual is None and flags == 0 and mod.weight.shape[1] == x.C:
-            # conv3x3(nearest x2 (x)) = four phase filters on x (Cin -> 4 Cout): same GEMM work, the input transform and the GEMM's
-            # A operand shrink 4x -- taken where x's own tile grid earns the same Winograd tile as the upsampled one
-            wl = phase_filter_tile(self.N, x.H, x.W, x.C, 4 * cout, self.m.winograd, self._wino_small(),
-                                   self.m.upsample_f72 and not self.training)
-            if wl == 7 and self._use_bf3(7, x.H, x.W, x.C, 4 * cout, h2=h2) not in ("p", "h"):
-                wl = 6                            # (F(7x7, 2x2) exists on the pre-split planes only)
-            if wl >= min(wm, 6):               # (m = 8 at the upsampled size does not beat the phase filters' 4x smaller input transform)
-                pw = _PackedWinograd(mod.weight, mod.bias, x.C, wl, bf3=self._use_bf3(wl, x.H, x.W, x.C, 4 * cout, h2=h2), phases=True)
-                self.convs.append(pw)
-                self._emit_winograd(x, x.C, pw, pre, False, x.H, x.W, None, 0, dest, 0)
-                return
-        if wm:
-            pw = _PackedWinograd(mod.weight, mod.bias, x.C, wm, bf3=self._use_bf3(
-                wm, H, W, x.C, cout, keeps_V=self._keeps_V(wm, H, W, x.C, mod.weight.shape[1], cout, upsample, False), h2=h2))
+        choice = getattr(pre, "choice", None)        # (decided by the emitter of this layer's input, which had to know it)
+        if choice is None:
+            choice = self._conv_choice(mod, x, upsample=upsample, flags=flags, has_residual=residual is not None,
+                                       bounded=getattr(pre, "h2", None) is not None, plain_input=pre is None or pre[0] is None)
+        if choice.kind in ("phases", "winograd"):
+            phases = choice.kind == "phases"        # (they run on x itself: H, W of the choice are x's, nothing is upsampled)
+            assert (flags & ~6) == 0 and not (phases and (residual is not None or flags))
+            pw = _PackedWinograd(mod.weight, mod.bias, x.C, choice.m, bf3=choice.bf3, phases=phases)
             self.convs.append(pw)
-            self._emit_winograd(x, x.C, pw, pre, upsample, H, W, residual, res_ld, dest, flags)
+            self._emit_winograd(x, x.C, pw, pre, upsample and not phases, choice.H, choice.W, residual, res_ld, dest, flags,
+                                keeps=choice.keeps_V)
             return
         assert not upsample
-        # (_gn_folds_into_transform mirrors the choices above; if the two ever diverge, the statistics reference a _GnPre carries in
-        # place of the coefficients must not reach a kernel that reads it as ``pre_scale`` -- round-4 advisor finding)
         if isinstance(pre, _GnPre):      # (a real error, not an assert: under python -O a statistics pointer would be read as coefficients)
             raise RuntimeError("bbdm_amd: a coefficient-folding producer reached a layer that is not a Winograd layer on the pre-split planes")
-        ks = mod.weight.shape[2] if mod.weight.dim() == 4 else 1
-        pixels = self.N * x.H * x.W
-        form = self._conv1x1_form(pixels, x.C, cout, getattr(pre, "h2", None) is not None) \
-            if (ks == 1 and (pre is None or pre[0] is None) and flags == 0) else None
-        if form is not None:
-            entry, layout, bounded = form
+        if choice.kind == "1x1":
+            entry, layout, bounded = choice.form
             pb = self._conv(mod, x.C, layout)
-            rec = self._emit_conv1x1(self._op, entry, x, pb, self._pref(pb.bias), residual, res_ld, dest, pixels, cout,
+            rec = self._emit_conv1x1(self._op, entry, x, pb, self._pref(pb.bias), residual, res_ld, dest, self.N * x.H * x.W, cout,
                                      pre.h2 if bounded else None)
             self._note_writer(dest, rec, None)
             return
@@ -1392,6 +1404,24 @@ class _Plan:
         return bool(m.side_stream_train and m.side_stream_wgrad) and pixels * cin * cout >= m.side_stream_wgrad_min_macs \
             and pixels <= m.side_stream_max_pixels
 
+    def _emit_skip(self, skip: nn.Conv2d, x: _View, out: _View, slot: int) -> Optional[tuple]:
+        """The 1x1 skip projection of a channel-changing ResBlock, out = skip(x).  On the fp16-pair planes it takes its bound from the
+        statistics the block's first GroupNorm took of the block input (accumulator ``slot``, complete by now; the bound launch stays on
+        the main stream, before a fork).  Returns its op range when it may run on the plan's second stream: the matrix-core forms, which
+        own no shared workspace."""
+        choice = self._takes_bound(skip, x)
+        xbound = self._stats_bound(slot) if choice is not None else None
+        choice = choice or self._conv_choice(skip, x)
+        k0 = len(self.ops)
+        self._emit_conv(x, skip, None, out, pre=_Pre(self.NO_PRE, h2=xbound, choice=choice))
+        return (k0, len(self.ops)) if choice.kind == "1x1" else None
+
+    def _takes_bound(self, mod, x: _View, has_residual: bool = False) -> Optional[_ConvChoice]:
+        """The choice of 1x1 layer ``mod`` on a plain, bounded ``x`` if that form takes the bound (the fp16-pair planes), else None: whoever
+        can give the layer's input a bound slot emits one iff the layer will read it."""
+        choice = self._conv_choice(mod, x, has_residual=has_residual, bounded=True)
+        return choice if (choice.form is not None and choice.form[2]) else None
+
     def _emit_res(self, rb: ResBlock, x: _View, dest: Optional[_View]) -> _View:
         """ResBlock._forward (openaimodel.py:258-278)."""
         N = self.N
@@ -1402,20 +1432,8 @@ class _Plan:
         # the captured graph, and join before the launch that adds it (the out conv's epilogue) -- it then runs beside the in conv's
         # launches instead of between them (UNetModel.side_stream_min_macs / _max_macs; kernels that own no shared workspace only)
         side, out = None, None
-        early_skip = isinstance(rb.skip_connection, nn.Conv2d) and rs == 0 and self._side_band(N * x.H * x.W, x.C, rb.out_channels)
-
-        def emit_early_skip():
-            # (after the block's first GroupNorm input has been emitted: the statistics of x are complete there, and the projection on
-            # the fp16-pair planes takes its bound from them -- the bound launch stays on the main stream, before the fork)
-            nonlocal side, out
-            out = dest if dest is not None else self._new(N, x.H, x.W, rb.out_channels)
-            xbound = self._stats_bound(s1) if (rb.skip_connection.weight.shape[2] == 1
-                                               and (self._conv1x1_h2_ok(N * x.H * x.W, x.C, rb.out_channels)
-                                                    or self._conv1x1_h2s_ok(N * x.H * x.W, x.C, rb.out_channels))) else None
-            k0 = len(self.ops)
-            self._emit_conv(x, rb.skip_connection, None, out, pre=_Pre(self.NO_PRE, h2=xbound) if xbound is not None else None)
-            if all(str(n) == "bbdm_conv1x1_bf3_f32" for n, _ in self.ops[k0:]):
-                side = (k0, len(self.ops))
+        skip = rb.skip_connection if isinstance(rb.skip_connection, nn.Conv2d) else None
+        early_skip = skip is not None and rs == 0 and self._side_band(N * x.H * x.W, x.C, rb.out_channels)
         # Up-sampling block, inference, both 3x3 convs on the Winograd path at the upsampled size: nothing is resampled explicitly.
         # GN -> SiLU -> nearest x2 folds into the input transform of in_layers[2] (index shift, csrc/winograd.hip: UP), and the skip path
         # x_upd(x) is the out conv's residual read at [h/2][w/2] (BBDM_CONV_RES_UPSAMPLE): the two gn_apply passes that wrote and
@@ -1427,20 +1445,21 @@ class _Plan:
         if rs == 0:
             a, pre1 = self._gn_input(x, rb.in_layers[0], None, silu=1, name="A", consumer=rb.in_layers[2])
             if early_skip:
-                emit_early_skip()
+                # (after the block's first GroupNorm input has been emitted: the statistics of x are complete there)
+                out = dest if dest is not None else self._new(N, x.H, x.W, rb.out_channels)
+                side = self._emit_skip(skip, x, out, s1)
         elif fold_up:
             a, pre1 = self._gn_input(x, rb.in_layers[0], None, silu=1, name="A", consumer=rb.in_layers[2], upsample=True)
         else:       # up / down blocks resample between the activation and the conv: explicit apply pass
             a, pre1 = self._gn_apply(x, rb.in_layers[0], None, silu=1, resample=rs, name="A"), None
-            if self._winograd_ok(rb.in_layers[2], a.H, a.W, a.C):
-                pre1 = _Pre(self.NO_PRE, h2=self._gn_bound(x, rb.in_layers[0], None))    # (pooled / copied values keep the bound)
+            choice = self._conv_choice(rb.in_layers[2], a, flags=0 if film else 2, has_residual=not film, bounded=self._h2_on(1))
+            if choice.kind == "winograd":
+                pre1 = _Pre(self.NO_PRE, h2=self._gn_bound(x, rb.in_layers[0], None), choice=choice)    # (pooled / copied values keep the bound)
         xr = x if (rs == 0 or fold_up) else self._gn_apply(x, None, None, 0, rs, name="XR")
         oh, ow = (2 * x.H, 2 * x.W) if fold_up else (a.H, a.W)
         h1 = self._tmp("H1", N, oh, ow, rb.out_channels)
-        if fold_up:
-            self._emit_conv(a, rb.in_layers[2], None, h1, pre=pre1, upsample=True)
-        elif film:
-            self._emit_conv(a, rb.in_layers[2], None, h1, pre=pre1)
+        if film:        # (fold_up: an up-sampling block with scale-shift)
+            self._emit_conv(a, rb.in_layers[2], None, h1, pre=pre1, upsample=fold_up)
         else:       # h = h + emb_out[..., None, None] (openaimodel.py:275): per-image row added in the conv epilogue
             self._emit_conv(a, rb.in_layers[2], _TensorRef(self.film, 4 * self.film_off[id(rb)]), h1,
                             res_ld=self.film_total, flags=2, pre=pre1)
@@ -1449,21 +1468,14 @@ class _Plan:
                                   consumer=rb.out_layers[3])
         if out is None:
             out = dest if dest is not None else self._new(N, oh, ow, rb.out_channels)
-        if isinstance(rb.skip_connection, nn.Conv2d):
-            if not early_skip:
-                # the projection reads the block input itself (pooled / copied for an up / down block: no larger): bounded by the
-                # statistics the block's first GroupNorm took of it (slot s1, complete by now)
-                xbound = self._stats_bound(s1) if (rb.skip_connection.weight.dim() == 4 and rb.skip_connection.weight.shape[2] == 1
-                                                   and (self._conv1x1_h2_ok(N * xr.H * xr.W, xr.C, rb.out_channels)
-                                                        or self._conv1x1_h2s_ok(N * xr.H * xr.W, xr.C, rb.out_channels))) else None
-                self._emit_conv(xr, rb.skip_connection, None, out, pre=_Pre(self.NO_PRE, h2=xbound) if xbound is not None else None)
+        if skip is not None:
+            if not early_skip:      # (the block input itself, pooled / copied for an up / down block: no larger)
+                self._emit_skip(skip, xr, out, s1)
             self._emit_conv(a2, rb.out_layers[3], out, out, pre=pre2)
             if side is not None:
                 self._side_ranges.append((side[0], side[1], len(self.ops) - 1))      # (.., the launch that reads the projection)
-        elif fold_up:
-            self._emit_conv(a2, rb.out_layers[3], xr, out, pre=pre2, flags=4)        # residual = x at half resolution
-        else:
-            self._emit_conv(a2, rb.out_layers[3], xr, out, pre=pre2)
+        else:           # (fold_up: residual = x at half resolution)
+            self._emit_conv(a2, rb.out_layers[3], xr, out, pre=pre2, flags=4 if fold_up else 0)
         if self.training:
             self.tape.append(("res", rb, x, a, xr, h1, a2, out, s1, s2, rs))
         return out
@@ -1477,13 +1489,14 @@ class _Plan:
         order = 1 if ab.use_new_attention_order else 0
         nb = int(self.lib.bbdm_attention_kv_planes_bytes(N, T, ab.num_heads, ch))
         attn_h2 = bool(nb and not self.training and getattr(self.m, "attn_h2", True) and self._h2_on(1) and (pre is None or pre[0] is None))
-        # proj_out reads the attention's output, a convex combination of value rows: |a| <= max |v| <= bound(qkv)
-        proj_h2 = self._conv1x1_h2_ok(N * T, C, C) or self._conv1x1_h2s_ok(N * T, C, C)
+        # the projections that would take a bound of their input get one (qkv: a = the GroupNorm output; proj_out reads the attention's
+        # output, a convex combination of value rows: |a| <= max |v| <= bound(qkv))
+        qkv_h2, proj_h2 = self._takes_bound(ab.qkv, a), self._takes_bound(ab.proj_out, x, has_residual=True)
         abound = qb = None
-        if (pre is None or pre[0] is None) and (attn_h2 or proj_h2 or self._conv1x1_h2_ok(N * T, C, 3 * C) or self._conv1x1_h2s_ok(N * T, C, 3 * C)):
+        if (pre is None or pre[0] is None) and (attn_h2 or proj_h2 or qkv_h2):
             abound = self._gn_bound(x, ab.norm, None)                         # (a materialised GroupNorm output: bounded by its coefficients)
-            if abound is not None and (self._conv1x1_h2_ok(N * T, C, 3 * C) or self._conv1x1_h2s_ok(N * T, C, 3 * C)):
-                pre = _Pre(self.NO_PRE, h2=abound)
+            if abound is not None and qkv_h2:
+                pre = _Pre(self.NO_PRE, h2=abound, choice=qkv_h2)
         qkv = self._tmp("QKV", N, x.H, x.W, 3 * C)
         self._emit_conv(a, ab.qkv, None, qkv, pre=pre)
         at = self._tmp("AT", N, x.H, x.W, C)
@@ -1514,7 +1527,7 @@ class _Plan:
         else:
             self._op("bbdm_attention_f32", qkv, qkv.ld, at, at.ld, lse, N, T, ab.num_heads, ch, order)
         out = dest if dest is not None else self._new(N, x.H, x.W, C)
-        self._emit_conv(at, ab.proj_out, x, out, pre=_Pre(self.NO_PRE, h2=qb) if (qb is not None and proj_h2) else None)
+        self._emit_conv(at, ab.proj_out, x, out, pre=_Pre(self.NO_PRE, h2=qb, choice=proj_h2) if (qb is not None and proj_h2) else None)
         if self.training:
             self.tape.append(("attn", ab, x, a, qkv, at, lse, out, s0))
         return out
@@ -1628,11 +1641,9 @@ class _Plan:
         if ds.use_conv:
             full = self._tmp("DSF", N, x.H, x.W, ds.out_channels)
             self._emit_conv(x, ds.op, None, full)
-            self._op("bbdm_groupnorm_apply_f32", full, full.ld, None, None, None, None, 0, out, out.ld, N, x.H, x.W,
-                     full.C, 1, 0.0, 0, 3)
+            self._resample(full, out, 3)
         else:
-            self._op("bbdm_groupnorm_apply_f32", x, x.ld, None, None, None, None, 0, out, out.ld, N, x.H, x.W, x.C, 1,
-                     0.0, 0, 1)
+            self._resample(x, out, 1)
         if self.training:
             self.tape.append(("down", ds, x, out))
         return out
@@ -1641,16 +1652,14 @@ class _Plan:
         """Upsample.forward (openaimodel.py:111-121): nearest x2, then an optional 3x3 conv."""
         N = self.N
         out = dest if dest is not None else self._new(N, x.H * 2, x.W * 2, us.out_channels)
+        u = None
         if us.use_conv and not self.training and self._winograd_ok(us.conv, 2 * x.H, 2 * x.W, x.C):
-            u = None                 # nearest x2 folded into the Winograd input transform: the 4x tensor never exists
-            self._emit_conv(x, us.conv, None, out, upsample=True)
+            self._emit_conv(x, us.conv, None, out, upsample=True)    # nearest x2 folded into the Winograd input transform: the 4x tensor never exists
         elif us.use_conv:
             u = self._gn_apply(x, None, None, 0, 2, name="XR")
             self._emit_conv(u, us.conv, None, out)
         else:
-            u = None
-            self._op("bbdm_groupnorm_apply_f32", x, x.ld, None, None, None, None, 0, out, out.ld, N, x.H, x.W, x.C, 1,
-                     0.0, 0, 2)
+            self._resample(x, out, 2)
         if self.training:
             self.tape.append(("up", us, x, u, out))
         return out
@@ -1671,6 +1680,326 @@ class _Plan:
         self.bops.append(rec)
         return rec
 
+    # While the gradient plan is emitted the plan carries: ``_gbufs`` / ``_written`` (the gradient twin of every persistent activation buffer,
+    # and which of them hold a gradient already), ``_ws_need`` (elements the workspaces _ws_f, _ws_f_side, _ws_d, _ws_d2 must hold) and
+    # ``_side_chains`` (second-stream launch ranges of the block being emitted, joined at its last GroupNorm backward).
+    def _gref(self, p):
+        return _Plan._GradRef(self, self.grad_off[id(p)])
+
+    def _gview(self, v: _View) -> _View:
+        b = self._gbufs.get(id(v.buf))
+        if b is None:
+            b = _Buf(v.buf.numel)
+            self._gbufs[id(v.buf)] = b
+            self.bufs.append(b)
+        return _View(b, v.off, v.ld, v.N, v.H, v.W, v.C)
+
+    def _first_write(self, v: _View) -> int:
+        """0 = overwrite (first gradient reaching this buffer), 1 = accumulate."""
+        acc = 1 if id(v.buf) in self._written else 0
+        self._written.add(id(v.buf))
+        return acc
+
+    def _grow(self, ws: str, n: int):
+        self._ws_need[ws] = max(self._ws_need[ws], n)
+
+    def _grad_resample(self, src: _View, dst: _View, acc: int, mode: int = 0):
+        """dst = (``acc``: +=) src copied (``mode`` 0), or the gradient of the forward resampling ``mode`` (_resample): the GroupNorm
+        backward pass without a GroupNorm."""
+        self._bop("bbdm_groupnorm_bwd_f32", None, 0, None, None, None, None, 0, None, 0, src, src.ld, dst, dst.ld, acc, None, None, None,
+                  0, None, dst.N, dst.H, dst.W, dst.C, 1, 0.0, 0, mode)
+
+    def _gn_bwd(self, gn, x: _View, slot, film_off, da: _View, dadd: Optional[_View], silu, rs, dx: _View, acc: int):
+        self._grow("_ws_d2", self.lib.bbdm_groupnorm_bwd_workspace_doubles(self.N, x.C, self.GROUPS))
+        film = None if film_off is None else _TensorRef(self.film, 4 * film_off)
+        dfilm = None if film_off is None else _TensorRef(self.dfilm, 4 * film_off)
+        self._bop("bbdm_groupnorm_bwd_f32", x, x.ld, _Plan._StatsRef(self, slot), self._pref(gn.weight), self._pref(gn.bias), film,
+                  self.film_total, da, da.ld, dadd, dadd.ld if dadd is not None else 0, dx, dx.ld, acc,
+                  self._gref(gn.weight), self._gref(gn.bias), dfilm, self.film_total, self._ws_d2, self.N, x.H, x.W, x.C, self.GROUPS,
+                  float(gn.eps), silu, rs)
+
+    def _conv_bwd(self, mod, x_in: _View, dy: _View, dx_name: str, dy_bound=None, side: bool = False, side_chain: bool = False) -> _View:
+        """Weight + bias gradient of conv / Linear ``mod``, then its data gradient into a scratch view.  dy: gradient of the conv output
+        (pitch >= Cout); ``dy_bound``: its bound slot where the caller measured it already (a gradient two layers read)."""
+        dy_bound = self._emit_wgrad(mod, x_in, dy, dy_bound, side, side_chain)
+        return self._emit_dgrad(mod, x_in, dy, dx_name, dy_bound)
+
+    def _emit_wgrad(self, mod, x_in: _View, dy: _View, dy_bound=None, side: bool = False, side_chain: bool = False):
+        """Weight + bias gradient.  ``side``: a 1x1 layer whose launches may run on the plan's second stream -- its weight gradient takes a
+        workspace of its own; ``side_chain``: a 3x3 layer whose Winograd-domain weight gradient on the kept planes may (that chain only).
+        Returns the bound slot of dY (fp16-pair planes): ``dy_bound``, or the one measured here, for the data gradient to share."""
+        m, N, lib = self.m, self.N, self.lib
+        w = mod.weight
+        cout, cin = w.shape[0], w.shape[1]
+        ks = w.shape[2] if w.dim() == 4 else 1
+        self._grow("_ws_f_side" if side else "_ws_f", lib.bbdm_conv_wgrad_workspace_floats(N, x_in.H, x_in.W, x_in.C, cout, ks))
+        if x_in.C == cin:
+            dw_dst = self._gref(w)
+        else:                                   # padded stem input: gradient of the padding channels is dropped
+            t = torch.empty(cout, x_in.C, ks, ks, dtype=torch.float32, device=self.device)
+            self._padded_wgrads.append((w, t, len(self.bops)))     # (.., index of the op that fills t: its segment copies it out)
+            dw_dst = _TensorRef(t)
+        wgm = (self._wgrad_tile(x_in.H, x_in.W, x_in.C, cout)
+               if (m.winograd_wgrad and ks == 3 and w.dim() == 4 and x_in.C == cin) else 0)
+        dbias = self._gref(mod.bias) if mod.bias is not None else None
+        saved = self._saved_V.get(id(w)) if wgm else None
+        if wgm == 8 and not (saved is not None and saved.m == 8 and saved.transposed):
+            # m = 8 exists on the kept transposed planes only: a layer that did not keep them re-transforms x at m <= 6
+            wgm = winograd_wgrad_tile(N, x_in.H, x_in.W, x_in.C, cout, min(6, m.winograd_wgrad))
+            saved = None
+        if saved is not None and saved.m == wgm and saved.transposed:
+            return self._wgrad_kept_planes(saved, x_in, dy, cout, dw_dst, dbias, dy_bound, side_chain)
+        if saved is not None and saved.m == wgm:
+            self._wgrad_kept_V(saved, x_in, dy, cout, dw_dst, dbias)
+        elif id(w) in self._fused_train:
+            raise RuntimeError("bbdm_amd: internal error: the activation of a fused-producer training layer was not kept")
+        elif wgm:
+            self._grow("_ws_f", lib.bbdm_winograd_wgrad_workspace_floats(wgm, N, x_in.H, x_in.W, x_in.C, cout))
+            self._bop("bbdm_conv3x3_winograd_wgrad_f32", wgm, x_in, x_in.ld, dy, dy.ld, dw_dst, dbias, self._ws_f, N,
+                      x_in.H, x_in.W, x_in.C, cout)
+        else:
+            self._bop("bbdm_conv_wgrad_f32", x_in, x_in.ld, dy, dy.ld, dw_dst, dbias, self._ws_f_side if side else self._ws_f,
+                      self._ws_f_side_floats if side else self._ws_f_floats, N, x_in.H, x_in.W, x_in.C, cout, ks)
+        return dy_bound
+
+    def _wgrad_kept_planes(self, saved: _SavedV, x_in: _View, dy: _View, cout: int, dw_dst, dbias, dy_bound, side_chain: bool):
+        """The forward kept the TRANSPOSED bf16 planes of V: dY transform (transposed planes of dM + the fp32 plane (1, 1)) -> the bf16x3
+        GEMM with the tiles as its K loop -> finish (csrc/gemm_bf3p.hip: bbdm_gemm_bf3p_tn_f32).  Returns the bound slot of dY."""
+        N, lib, wgm = self.N, self.lib, saved.m
+        P, Tp = wino_planes(wgm), lib.bbdm_winograd_tiles(wgm, N, x_in.H, x_in.W)
+        T = wino_tiles(wgm, N, x_in.H, x_in.W)
+        splits = lib.bbdm_gemm_bf3p_tn_splits(P, Tp, x_in.C, cout)
+        w_h2 = saved.bound is not None          # the forward kept V^T as fp16 pairs: dM on the pair too, under dY's measured maximum
+        if w_h2:
+            dy_bound = dy_bound or self._dy_bound(dy)      # (on the main stream, before a side chain forks)
+        n_dmt = ((lib.bbdm_gemm_h2p_tn_bt_bytes if w_h2 else lib.bbdm_gemm_bf3p_tn_bt_bytes)(P, Tp, cout) + 3) // 4          # floats
+        o_dm11 = n_dmt
+        o_du = o_dm11 + Tp * cout
+        o_acc = (o_du + splits * P * x_in.C * cout + 1) & ~1
+        # ``side_chain`` (a ResBlock's 3x3 layer, UNetModel.side_stream_wgrad): the three launches of this weight gradient read dY,
+        # the kept planes and their own workspace only -- on the plan's second stream beside the data gradient of the same
+        # layer (whose tile GEMM leaves its last round half empty, DESIGN.md 5); joined at the end of the block
+        chain = side_chain and self._side_band3(N * x_in.H * x_in.W, x_in.C, cout)
+        self._grow("_ws_f_side" if chain else "_ws_f", o_acc + 8 * cout + 2)        # (+ the column sums' limb cells: 4 x 8 B per channel)
+        wsf = self._ws_f_side if chain else self._ws_f
+        dMt, dm11, dU = _TensorRef(wsf, 0), _TensorRef(wsf, 4 * o_dm11), _TensorRef(wsf, 4 * o_du)
+        k_chain = len(self.bops)
+        if w_h2:
+            self._bop(_OpName("bbdm_winograd_dy_transform_bf3p_f32", "bbdm_winograd_dy_transform_h2p_f32"), wgm, dy, dy.ld, dMt, dm11,
+                      N, x_in.H, x_in.W, cout, dy_bound)
+            self._bop(_OpName("bbdm_gemm_bf3p_tn_f32", "bbdm_gemm_h2p_tn_f32"), saved.v, dMt, dU, P, Tp, x_in.C, cout,
+                      saved.bound, float(lib.bbdm_winograd_input_gain(wgm)), dy_bound, float(lib.bbdm_winograd_dy_gain(wgm)))
+        else:
+            self._bop("bbdm_winograd_dy_transform_bf3p_f32", wgm, dy, dy.ld, dMt, dm11, N, x_in.H, x_in.W, cout)
+            self._bop("bbdm_gemm_bf3p_tn_f32", saved.v, dMt, dU, P, Tp, x_in.C, cout)
+        if dbias is not None and cout % 4 == 0:
+            # ... + the bias gradient in the same launch: column sums of dM's plane (1, 1) = the tile sums of dY
+            self._bop("bbdm_winograd_wgrad_finish_bias_f32", wgm, dU, splits, dw_dst, x_in.C, cout, dm11, T, dbias)
+        else:
+            self._bop("bbdm_winograd_wgrad_finish_f32", wgm, dU, splits, dw_dst, x_in.C, cout)
+            if dbias is not None:
+                self._bop("bbdm_colsum_f32", dm11, cout, _TensorRef(wsf, 4 * o_acc), dbias, T, cout)
+        if chain:
+            self._side_chains.append((k_chain, len(self.bops)))
+        return dy_bound
+
+    def _wgrad_kept_V(self, saved: _SavedV, x_in: _View, dy: _View, cout: int, dw_dst, dbias):
+        """The forward kept this layer's fp32 V: dY transform -> TN GEMM -> finish (the stages bbdm_conv3x3_winograd_wgrad_f32 chains)."""
+        N, lib, wgm = self.N, self.lib, saved.m
+        P, Tp = wino_planes(wgm), lib.bbdm_winograd_tiles(wgm, N, x_in.H, x_in.W)
+        T = wino_tiles(wgm, N, x_in.H, x_in.W)
+        splits = lib.bbdm_gemm_tn_splits(P, T, x_in.C, cout)
+        o_du = P * Tp * cout
+        o_acc = (o_du + splits * P * x_in.C * cout + 1) & ~1
+        self._grow("_ws_f", o_acc + 8 * cout + 2)        # (+ the column sums' limb cells: 4 x 8 B per channel)
+        dM, dU = _TensorRef(self._ws_f, 0), _TensorRef(self._ws_f, 4 * o_du)
+        self._bop("bbdm_winograd_dy_transform_f32", wgm, dy, dy.ld, dM, N, x_in.H, x_in.W, cout)
+        self._bop("bbdm_gemm_tn_batched_f32", saved.v, x_in.C, Tp * x_in.C, dM, cout, Tp * cout, dU, P, T, x_in.C, cout)
+        self._bop("bbdm_winograd_wgrad_finish_f32", wgm, dU, splits, dw_dst, x_in.C, cout)
+        if dbias is not None:       # column sums of the plane dM_(1,1) = the tile sums of dY (csrc/winograd_wgrad.hip)
+            self._bop("bbdm_colsum_f32", _TensorRef(self._ws_f, 4 * (wgm + 3) * Tp * cout), cout,
+                      _TensorRef(self._ws_f, 4 * o_acc), dbias, T, cout)
+
+    def _dgrad1x1_form(self, mod, x_in: _View, dy: _View):
+        """The matrix-core form of the data gradient dX = dY W of a 1x1 layer (_conv1x1_form), or None = the direct kernel."""
+        w = mod.weight
+        if (w.shape[2] if w.dim() == 4 else 1) != 1 or x_in.C != w.shape[1]:
+            return None
+        return self._conv1x1_form(x_in.N * x_in.H * x_in.W, dy.C, x_in.C, True, dy_ld=dy.ld)
+
+    def _emit_dgrad(self, mod, x_in: _View, dy: _View, dx_name: str, dy_bound=None) -> _View:
+        """Data gradient of conv / Linear ``mod`` into the scratch view ``dx_name``: the forward convolution of dY with the flipped
+        filters.  ``dy_bound``: the bound slot of dY if one was measured already (_emit_wgrad), else it is measured where a form needs it."""
+        m, N = self.m, self.N
+        w = mod.weight
+        ks = w.shape[2] if w.dim() == 4 else 1
+        dx = self._tmp(dx_name, N, x_in.H, x_in.W, x_in.C)
+        wm = (winograd_tile(N, x_in.H, x_in.W, dy.C, x_in.C, m.winograd, small=self._wino_small(), allow8=self._allow8(1))
+              if (m.winograd and ks == 3 and w.dim() == 4 and x_in.C == w.shape[1]) else 0)
+        if wm:
+            mode = self._use_bf3(wm, x_in.H, x_in.W, dy.C, x_in.C, h2=self._h2_on(2) and dy.C % 4 == 0 and dy.ld % 4 == 0)
+            pk = _PackedWinograd(w, None, dy.C, wm, dgrad=True, bf3=mode)
+            self.dconvs.append(pk)
+            # fp16-pair planes: dY under its measured maximum (UNetModel.gemm_h2_train = 2)
+            pre_dy = _Pre(self.NO_PRE, h2=dy_bound or self._dy_bound(dy)) if mode == "h" else None
+            self._emit_winograd(dy, dy.C, pk, pre_dy, False, x_in.H, x_in.W, None, 0, dx, 0, bwd=True)
+            return dx
+        form = self._dgrad1x1_form(mod, x_in, dy)
+        if form is not None:
+            # wide 1x1 layers: dX = dY W on the matrix core like their forward -- on the fp16 pair with dY under its measured maximum
+            # (as the 3x3 layers' data gradient), else on the bf16x3 GEMM
+            entry, layout, bounded = form
+            pk = _PackedConv(w, None, dy.C, layout, dgrad=True)
+            self.dconvs.append(pk)
+            if bounded:
+                dy_bound = dy_bound or self._dy_bound(dy)
+            self._emit_conv1x1(self._bop, entry, dy, pk, None, None, 0, dx, x_in.N * x_in.H * x_in.W, x_in.C, dy_bound if bounded else None)
+            return dx
+        pk = _PackedConv(w, None, dy.C, dgrad=True)
+        self.dconvs.append(pk)
+        self._conv_ws_need = max(self._conv_ws_need, self.lib.bbdm_conv_splitk_workspace_floats(N, x_in.H, x_in.W, dy.C, x_in.C, ks))
+        self._bop("bbdm_conv2d_nhwc_f32", dy, dy.ld, _TensorRef(pk.packed), None, None, 0, dx, dx.ld, 0,
+                  self._conv_ws, self._conv_ws_floats, None, None, 0, 0, N, x_in.H, x_in.W, dy.C, x_in.C, ks)
+        return dx
+
+    # ---- one method per tape record kind (dispatched by _emit_backward; _record_params switches on the same kinds) ----
+    def _bwd_head(self, seq, h, a, slot):
+        N, cout = self.N, self.m.out_channels
+        cpad = _round4(cout)
+        dy = self._tmp("DOUT", N, a.H, a.W, cpad)
+        self._bop("bbdm_nchw_to_nhwc_f32", _TensorRef(self.dout_nchw), cout, None, 0, dy, dy.ld, cpad, N, a.H, a.W)
+        da = self._conv_bwd(seq[2], a, _View(dy.buf, 0, dy.ld, N, a.H, a.W, cpad), "DA")
+        self._gn_bwd(seq[0], h, slot, None, da, None, 1, 0, self._gview(h), self._first_write(h))
+
+    def _bwd_res(self, rb, x, a, xr, h1, a2, out, s1, s2, rs):
+        N = self.N
+        dout = self._gview(out)
+        dxr, bside = dout, None
+        # dOut is read by the skip projection's and by the out conv's gradients: its maximum is measured once, on the main stream
+        dref = self._dy_bound(dout) if (self._h2_on(2) and dout.C % 4 == 0 and dout.ld % 4 == 0) else None
+        skip = rb.skip_connection
+        if isinstance(skip, nn.Conv2d):
+            # the projection's gradients read only dOut (complete before this block's backward starts) and the block input: on the
+            # second stream beside the block's own chain; joined before the launch that adds dXr (the last GroupNorm backward) --
+            # only where the data gradient takes a matrix-core form (the direct kernel owns a shared workspace) that the bf16x3 GEMM
+            # could take as well; the weight gradient then gets a workspace of its own
+            px = N * xr.H * xr.W
+            sb = bool(rs == 0 and self._side_band(px, xr.C, rb.out_channels) and self._dgrad1x1_form(skip, xr, dout) is not None
+                      and self.lib.bbdm_gemm_bf3_supported(px, dout.C, xr.C))
+            k0 = len(self.bops)
+            dxr = self._conv_bwd(skip, xr, dout, "DXR", dy_bound=dref, side=sb)
+            bside = (k0, len(self.bops)) if sb else None
+        self._side_chains.clear()
+        da2 = self._conv_bwd(rb.out_layers[3], a2, dout, "DA2", dy_bound=dref, side_chain=True)
+        dh1 = self._tmp("DH1", N, h1.H, h1.W, h1.C)
+        film = rb.use_scale_shift_norm
+        self._gn_bwd(rb.out_layers[0], h1, s2, self.film_off[id(rb)] if film else None, da2, None, 1, 0, dh1, 0)
+        if not film:    # d emb_out[n, c] = sum_hw d(h + emb_out)
+            self._grow("_ws_d", 4 * N * h1.C)        # limb cells (csrc/stats_acc.h): 4 words per sum
+            self._bop("bbdm_colsum_batched_f32", dh1, dh1.ld, self._ws_d,
+                      _TensorRef(self.dfilm, 4 * self.film_off[id(rb)]), self.film_total, N, h1.H * h1.W, h1.C)
+        da = self._conv_bwd(rb.in_layers[2], a, dh1, "DA", side_chain=True)
+        dx = self._gview(x)
+        for k0, k1 in ([bside] if bside is not None else []) + self._side_chains:
+            self._bside_ranges.append((k0, k1, len(self.bops)))
+        self._side_chains.clear()
+        self._gn_bwd(rb.in_layers[0], x, s1, None, da, dxr, 1, rs, dx, self._first_write(x))
+
+    def _bwd_attn(self, ab, x, a, qkv, at, lse, out, s0):
+        N, T, C = self.N, x.H * x.W, x.C
+        dout = self._gview(out)
+        dat = self._conv_bwd(ab.proj_out, at, dout, "DAT")
+        dqkv = self._tmp("DQKV", N, x.H, x.W, 3 * C)
+        dwork = _TensorRef(torch.empty(N * ab.num_heads * T, dtype=torch.float32, device=self.device))
+        self._bop("bbdm_attention_bwd_f32", qkv, qkv.ld, at, at.ld, dat, dat.ld, lse, dwork, dqkv, dqkv.ld, N, T,
+                  ab.num_heads, C // ab.num_heads, 1 if ab.use_new_attention_order else 0)
+        da = self._conv_bwd(ab.qkv, a, dqkv, "DA")
+        self._gn_bwd(ab.norm, x, s0, None, da, dout, 0, 0, self._gview(x), self._first_write(x))
+
+    ST_RING = ("ST_DHA", "ST_DHB", "ST_DHC")        # gradient of a SpatialTransformer's residual stream: three live at most
+
+    def _st_ln_bwd(self, ln_mod, xin: _View, dy: _View, dadd: _View) -> _View:
+        """LayerNorm backward into the next buffer of the ring: d xin = LN'(dy) + dadd."""
+        self._grow("_ws_d2", 8 * xin.C)      # [2][C] limb cells of 4 words
+        self._st_turn = (self._st_turn + 1) % 3
+        dxv = self._tmp(self.ST_RING[self._st_turn], xin.N, xin.H, xin.W, xin.C)
+        self._bop("bbdm_layernorm_bwd_f32", xin, xin.ld, self._pref(ln_mod.weight), dy, dy.ld, dadd, dadd.ld, dxv,
+                  dxv.ld, self._gref(ln_mod.weight), self._gref(ln_mod.bias), self._ws_d2, xin.N * xin.H * xin.W, xin.C, float(ln_mod.eps))
+        return dxv
+
+    def _st_attn_bwd(self, st, arec, dres: _View, ctx) -> _View:
+        """dres = gradient of (to_out(attention) + residual); returns the gradient of the LayerNorm output."""
+        att, xin, kv_src, q, kview, vview, at, lse = arec
+        N, H, W, heads, inner = self.N, xin.H, xin.W, st.n_heads, st.n_heads * st.d_head
+        dat = self._conv_bwd(att.to_out[0], at, dres, "ST_DAT")
+        dq = self._tmp("ST_DQ", N, H, W, inner)
+        dkv = self._tmp("ST_DKV", kv_src.N, kv_src.H, kv_src.W, 2 * inner)
+        dk = _View(dkv.buf, 0, dkv.ld, kv_src.N, kv_src.H, kv_src.W, inner)
+        dv = _View(dkv.buf, inner, dkv.ld, kv_src.N, kv_src.H, kv_src.W, inner)
+        dwork = _TensorRef(torch.empty(N * heads * H * W, dtype=torch.float32, device=self.device))
+        self._bop("bbdm_cross_attention_bwd_f32", q, q.ld, kview, vview, kview.ld, at, at.ld, dat, dat.ld, lse, dwork,
+                  dq, dq.ld, dk, dv, dkv.ld, N, H * W, kv_src.H * kv_src.W, heads, st.d_head)
+        dln = self._conv_bwd(att.to_q, xin, dq, "ST_DLN")
+        dsk = self._conv_bwd(att.to_k, kv_src, dk, "ST_DSK")
+        dsv = self._conv_bwd(att.to_v, kv_src, dv, "ST_DSV")
+        if kv_src is ctx:                       # context tokens: their gradient leaves through the UNet's d input
+            first = self.dctx_tokens is None
+            if first:
+                self.dctx_tokens = self._new(ctx.N, ctx.H, ctx.W, ctx.C)
+            self._grad_resample(dsk, self.dctx_tokens, 0 if first else 1)
+            self._grad_resample(dsv, self.dctx_tokens, 1)
+        else:                                   # self-attention: keys and values come from the same LayerNorm output
+            self._grad_resample(dsk, dln, 1)
+            self._grad_resample(dsv, dln, 1)
+        return dln
+
+    def _bwd_st(self, st, x, a, s0, blocks, h_last, out, ctx):
+        """SpatialTransformer (attention.py:249-263) in reverse; BasicTransformerBlock._forward (attention.py:215-218):
+        x = attn1(norm1(x)) + x;  x = attn2(norm2(x), context) + x;  x = ff(norm3(x)) + x"""
+        N, H, W = self.N, x.H, x.W
+        dout = self._gview(out)
+        self._st_turn = 0
+        dh = self._conv_bwd(st.proj_out, h_last, dout, self.ST_RING[0])
+        for blk, h_in, rec1, h1, rec2, h2, ln3, pr, gl in reversed(blocks):
+            dgl = self._conv_bwd(blk.ff.net[2], gl, dh, "ST_DGL")
+            dpr = self._tmp("ST_DPR", N, H, W, pr.C)
+            self._bop("bbdm_geglu_bwd_f32", pr, pr.ld, dgl, dgl.ld, dpr, dpr.ld, N * H * W, gl.C)
+            dln3 = self._conv_bwd(blk.ff.net[0].proj, ln3, dpr, "ST_DLN")
+            dh2 = self._st_ln_bwd(blk.norm3, h2, dln3, dh)
+            dln2 = self._st_attn_bwd(st, rec2, dh2, ctx)
+            dh1 = self._st_ln_bwd(blk.norm2, h1, dln2, dh2)
+            dln1 = self._st_attn_bwd(st, rec1, dh1, ctx)
+            dh = self._st_ln_bwd(blk.norm1, h_in, dln1, dh1)
+        da = self._conv_bwd(st.proj_in, a, dh, "DA")
+        self._gn_bwd(st.norm, x, s0, None, da, dout, 0, 0, self._gview(x), self._first_write(x))
+
+    def _bwd_down(self, ds, x, out):
+        dout, dx = self._gview(out), self._gview(x)
+        if ds.use_conv:
+            dfull = self._tmp("DDSF", self.N, x.H, x.W, ds.out_channels)
+            self._grad_resample(dout, dfull, 0, 3)
+            dxs = self._conv_bwd(ds.op, x, dfull, "DA")
+            self._grad_resample(dxs, dx, self._first_write(x))
+        else:
+            self._grad_resample(dout, dx, self._first_write(x), 1)
+
+    def _bwd_up(self, us, x, u, out):
+        dout, dx = self._gview(out), self._gview(x)
+        du = self._conv_bwd(us.conv, u, dout, "DA") if us.use_conv else dout
+        self._grad_resample(du, dx, self._first_write(x), 2)
+
+    def _bwd_stem(self, conv, x, out):
+        dout = self._gview(out)
+        self._emit_wgrad(conv, x, dout)
+        # d input (only when x / context require grad, e.g. a trainable SpatialRescaler context): own op list
+        main, self.bops = self.bops, []
+        pk = _PackedConv(conv.weight, None, dout.C, dgrad=True)
+        self.dconvs.append(pk)
+        self.dx0 = self._tmp("DX0", self.N, x.H, x.W, x.C)
+        self._bop("bbdm_conv2d_nhwc_f32", dout, dout.ld, _TensorRef(pk.packed), None, None, 0, self.dx0,
+                  self.dx0.ld, 0, None, 0, None, None, 0, 0, self.N, x.H, x.W, dout.C, x.C, 3)
+        self.bops_x0, self.bops = self.bops, main
+
     def _emit_backward(self, x0: _View):
         """Walk the tape in reverse and emit the gradient ops.
 
@@ -1680,7 +2009,6 @@ class _Plan:
         accumulation -- the concat consumer always runs first in reverse order and writes the whole buffer.
         """
         m, N, lib, dev = self.m, self.N, self.lib, self.device
-        G = self.GROUPS
         # parameter -> offset in the flat gradient buffer.  The FiLM projections (every ResBlock's emb_layers.1) come FIRST, weights then
         # biases, in the order of the concatenated [film_total x 4 mc] GEMM that computes their gradients (_backward_embedding): that GEMM
         # then writes the parameter gradients in place (round 3 copied 2 x 21 slices out of a scratch tensor per micro-step); the other
@@ -1700,354 +2028,31 @@ class _Plan:
                 off += p.numel()
         self.grad_total = off
         self._flat_grad = None
-        gref = lambda p: _Plan._GradRef(self, self.grad_off[id(p)])
 
-        gbufs: Dict[int, _Buf] = {}
-        written = set()
-
-        def gview(v: _View) -> _View:
-            b = gbufs.get(id(v.buf))
-            if b is None:
-                b = _Buf(v.buf.numel)
-                gbufs[id(v.buf)] = b
-                self.bufs.append(b)
-            return _View(b, v.off, v.ld, v.N, v.H, v.W, v.C)
-
-        def first_write(v: _View) -> int:
-            """0 = overwrite (first gradient reaching this buffer), 1 = accumulate."""
-            k = id(v.buf)
-            acc = 1 if k in written else 0
-            written.add(k)
-            return acc
-
-        ws_floats, ws_doubles, colsum_c, ws_side_floats = [1], [1], [1], [1]
-        side_chains: List[tuple] = []       # second-stream launch ranges of the block being emitted (joined at its last GroupNorm backward)
-
-        def sstat(slot):
-            return _Plan._StatsRef(self, slot)
-
-        def conv_bwd(mod, x_in: _View, dy: _View, need_dx: bool, dx_name: str, cin_true=None, side: bool = False,
-                     side_chain: bool = False, dy_bound=None):
-            """wgrad + bias grad (+ dgrad into a scratch view).  dy: gradient of the conv output (pitch >= Cout).  ``side``: a 1x1
-            layer whose launches may run on the plan's second stream -- its weight gradient takes a workspace of its own;
-            ``side_chain``: a 3x3 layer whose Winograd-domain weight gradient on the kept planes may (that chain only)."""
-            w = mod.weight
-            cout, cin = w.shape[0], w.shape[1]
-            ks = w.shape[2] if w.dim() == 4 else 1
-            dy_ref = [dy_bound]                      # the bound slot of dY (fp16-pair planes): measured once, shared by wgrad and dgrad
-                                                     # (``dy_bound``: the caller measured it already -- a gradient two layers read)
-            wsn = ws_side_floats if side else ws_floats
-            wsn[0] = max(wsn[0], lib.bbdm_conv_wgrad_workspace_floats(N, x_in.H, x_in.W, x_in.C, cout, ks))
-            if x_in.C == cin:
-                dw_dst = gref(w)
-            else:                                   # padded stem input: gradient of the padding channels is dropped
-                t = torch.empty(cout, x_in.C, ks, ks, dtype=torch.float32, device=dev)
-                self._padded_wgrads.append((w, t, len(self.bops)))     # (.., index of the op that fills t: its segment copies it out)
-                dw_dst = _TensorRef(t)
-            wgm = (self._wgrad_tile(x_in.H, x_in.W, x_in.C, cout)
-                   if (m.winograd_wgrad and ks == 3 and w.dim() == 4 and x_in.C == cin) else 0)
-            dbias = gref(mod.bias) if mod.bias is not None else None
-            saved = self._saved_V.get(id(w)) if wgm else None
-            if wgm == 8 and not (saved is not None and saved[1] == 8 and len(saved) > 2):
-                # m = 8 exists on the kept transposed planes only: a layer that did not keep them re-transforms x at m <= 6
-                wgm = winograd_wgrad_tile(N, x_in.H, x_in.W, x_in.C, cout, min(6, m.winograd_wgrad))
-                saved = None
-            if saved is not None and saved[1] == wgm and len(saved) > 2:
-                # the forward kept the TRANSPOSED bf16 planes of V: dY transform (transposed planes of dM + the fp32 plane (1, 1)) ->
-                # the bf16x3 GEMM with the tiles as its K loop -> finish (csrc/gemm_bf3p.hip: bbdm_gemm_bf3p_tn_f32)
-                P, Tp = wino_planes(wgm), lib.bbdm_winograd_tiles(wgm, N, x_in.H, x_in.W)
-                T = wino_tiles(wgm, N, x_in.H, x_in.W)
-                splits = lib.bbdm_gemm_bf3p_tn_splits(P, Tp, x_in.C, cout)
-                w_h2 = len(saved) > 3                    # the forward kept V^T as fp16 pairs: dM on the pair too, under dY's measured maximum
-                if w_h2:
-                    dy_ref[0] = dy_ref[0] or self._dy_bound(dy)      # (on the main stream, before a side chain forks)
-                n_dmt = ((lib.bbdm_gemm_h2p_tn_bt_bytes if w_h2 else lib.bbdm_gemm_bf3p_tn_bt_bytes)(P, Tp, cout) + 3) // 4          # floats
-                o_dm11 = n_dmt
-                o_du = o_dm11 + Tp * cout
-                o_acc = (o_du + splits * P * x_in.C * cout + 1) & ~1
-                # ``side`` (a ResBlock's 3x3 layer, UNetModel.side_stream_wgrad): the three launches of this weight gradient read dY,
-                # the kept planes and their own workspace only -- on the plan's second stream beside the data gradient of the same
-                # layer (whose tile GEMM leaves its last round half empty, DESIGN.md 5); joined at the end of the block
-                chain = side_chain and self._side_band3(N * x_in.H * x_in.W, x_in.C, cout)
-                wsn = ws_side_floats if chain else ws_floats
-                wsn[0] = max(wsn[0], o_acc + 8 * cout + 2)        # (+ the column sums' limb cells: 4 x 8 B per channel)
-                wsf = self._ws_f_side if chain else self._ws_f
-                dMt, dm11, dU = _TensorRef(wsf, 0), _TensorRef(wsf, 4 * o_dm11), _TensorRef(wsf, 4 * o_du)
-                k_chain = len(self.bops)
-                if w_h2:
-                    self._bop(_OpName("bbdm_winograd_dy_transform_bf3p_f32", "bbdm_winograd_dy_transform_h2p_f32"), wgm, dy, dy.ld, dMt, dm11,
-                              N, x_in.H, x_in.W, cout, dy_ref[0])
-                    self._bop(_OpName("bbdm_gemm_bf3p_tn_f32", "bbdm_gemm_h2p_tn_f32"), saved[0], dMt, dU, P, Tp, x_in.C, cout,
-                              saved[3], float(lib.bbdm_winograd_input_gain(wgm)), dy_ref[0], float(lib.bbdm_winograd_dy_gain(wgm)))
-                else:
-                    self._bop("bbdm_winograd_dy_transform_bf3p_f32", wgm, dy, dy.ld, dMt, dm11, N, x_in.H, x_in.W, cout)
-                    self._bop("bbdm_gemm_bf3p_tn_f32", saved[0], dMt, dU, P, Tp, x_in.C, cout)
-                if dbias is not None and cout % 4 == 0:
-                    # ... + the bias gradient in the same launch: column sums of dM's plane (1, 1) = the tile sums of dY
-                    self._bop("bbdm_winograd_wgrad_finish_bias_f32", wgm, dU, splits, dw_dst, x_in.C, cout, dm11, T, dbias)
-                else:
-                    self._bop("bbdm_winograd_wgrad_finish_f32", wgm, dU, splits, dw_dst, x_in.C, cout)
-                    if dbias is not None:
-                        self._bop("bbdm_colsum_f32", dm11, cout, _TensorRef(wsf, 4 * o_acc), dbias, T, cout)
-                if chain:
-                    side_chains.append((k_chain, len(self.bops)))
-            elif saved is not None and saved[1] == wgm:
-                # the forward kept this layer's V: dY transform -> TN GEMM -> finish (the stages bbdm_conv3x3_winograd_wgrad_f32 chains)
-                P, Tp = wino_planes(wgm), lib.bbdm_winograd_tiles(wgm, N, x_in.H, x_in.W)
-                T = wino_tiles(wgm, N, x_in.H, x_in.W)
-                splits = lib.bbdm_gemm_tn_splits(P, T, x_in.C, cout)
-                o_du = P * Tp * cout
-                o_acc = (o_du + splits * P * x_in.C * cout + 1) & ~1
-                ws_floats[0] = max(ws_floats[0], o_acc + 8 * cout + 2)        # (+ the column sums' limb cells: 4 x 8 B per channel)
-                dM, dU = _TensorRef(self._ws_f, 0), _TensorRef(self._ws_f, 4 * o_du)
-                self._bop("bbdm_winograd_dy_transform_f32", wgm, dy, dy.ld, dM, N, x_in.H, x_in.W, cout)
-                self._bop("bbdm_gemm_tn_batched_f32", saved[0], x_in.C, Tp * x_in.C, dM, cout, Tp * cout, dU, P, T, x_in.C, cout)
-                self._bop("bbdm_winograd_wgrad_finish_f32", wgm, dU, splits, dw_dst, x_in.C, cout)
-                if dbias is not None:       # column sums of the plane dM_(1,1) = the tile sums of dY (csrc/winograd_wgrad.hip)
-                    self._bop("bbdm_colsum_f32", _TensorRef(self._ws_f, 4 * (wgm + 3) * Tp * cout), cout,
-                              _TensorRef(self._ws_f, 4 * o_acc), dbias, T, cout)
-            elif id(w) in self._fused_train:
-                raise RuntimeError("bbdm_amd: internal error: the activation of a fused-producer training layer was not kept")
-            elif wgm:
-                ws_floats[0] = max(ws_floats[0], lib.bbdm_winograd_wgrad_workspace_floats(wgm, N, x_in.H, x_in.W, x_in.C, cout))
-                self._bop("bbdm_conv3x3_winograd_wgrad_f32", wgm, x_in, x_in.ld, dy, dy.ld, dw_dst, dbias, self._ws_f, N,
-                          x_in.H, x_in.W, x_in.C, cout)
-            else:
-                self._bop("bbdm_conv_wgrad_f32", x_in, x_in.ld, dy, dy.ld, dw_dst, dbias, self._ws_f_side if side else self._ws_f,
-                          self._ws_f_side_floats if side else self._ws_f_floats, N, x_in.H, x_in.W, x_in.C, cout, ks)
-            if not need_dx:
-                return None
-            dx = self._tmp(dx_name, N, x_in.H, x_in.W, x_in.C)
-            wm = (winograd_tile(N, x_in.H, x_in.W, dy.C, x_in.C, m.winograd, small=self._wino_small(), allow8=self._allow8(1))
-                  if (m.winograd and ks == 3 and w.dim() == 4 and x_in.C == cin) else 0)
-            if wm:
-                mode = self._use_bf3(wm, x_in.H, x_in.W, dy.C, x_in.C, h2=self._h2_on(2) and dy.C % 4 == 0 and dy.ld % 4 == 0)
-                pk = _PackedWinograd(w, None, dy.C, wm, dgrad=True, bf3=mode)
-                self.dconvs.append(pk)
-                # fp16-pair planes: dY under its measured maximum (UNetModel.gemm_h2_train = 2)
-                pre_dy = _Pre(self.NO_PRE, h2=dy_ref[0] or self._dy_bound(dy)) if mode == "h" else None
-                self._emit_winograd(dy, dy.C, pk, pre_dy, False, x_in.H, x_in.W, None, 0, dx, 0, bwd=True)
-                return dx
-            pixels = x_in.N * x_in.H * x_in.W
-            if (ks == 1 and x_in.C == cin and self._h2_on(2) and getattr(m, "conv1x1_h2", True) and dy.C % 16 == 0 and dy.ld % 4 == 0
-                    and x_in.C % 4 == 0 and (pixels // 256) * -(-x_in.C // 128) >= m.bf3_min_tiles):
-                # wide 1x1 layers on the fp16 pair: dX = dY W with dY under its measured maximum (as the 3x3 layers' data gradient)
-                pk = _PackedConv(w, None, dy.C, "h", dgrad=True)
-                self.dconvs.append(pk)
-                dy_ref[0] = dy_ref[0] or self._dy_bound(dy)
-                self._emit_conv1x1(self._bop, "bbdm_conv1x1_h2q_f32", dy, pk, None, None, 0, dx, pixels, x_in.C, dy_ref[0])
-                return dx
-            if (ks == 1 and m.gemm_bf3 and x_in.C == cin and lib.bbdm_gemm_bf3_supported(pixels, dy.C, x_in.C)
-                    and (pixels // 256) * -(-x_in.C // 128) >= m.bf3_min_tiles):
-                q = (-(-x_in.C // 128) * 128) % 256 == 0
-                pk = _PackedConv(w, None, dy.C, "p" if q else True, dgrad=True)  # wide 1x1 layers: dX = dY W on the bf16x3 GEMM, like their forward
-                self.dconvs.append(pk)
-                self._emit_conv1x1(self._bop, "bbdm_conv1x1_bf3q_f32" if q else "bbdm_conv1x1_bf3_f32", dy, pk, None, None, 0, dx, pixels, x_in.C)
-                return dx
-            pk = _PackedConv(w, None, dy.C, dgrad=True)
-            self.dconvs.append(pk)
-            self._conv_ws_need = max(self._conv_ws_need,
-                                     lib.bbdm_conv_splitk_workspace_floats(N, x_in.H, x_in.W, dy.C, x_in.C, ks))
-            self._bop("bbdm_conv2d_nhwc_f32", dy, dy.ld, _TensorRef(pk.packed), None, None, 0, dx, dx.ld, 0,
-                      self._conv_ws, self._conv_ws_floats, None, None, 0, 0, N, x_in.H, x_in.W, dy.C, x_in.C, ks)
-            return dx
-
-        def gn_bwd(gn, x: _View, slot, film_off, da: _View, dadd: Optional[_View], silu, rs, dx: _View, acc: int):
-            ws_doubles[0] = max(ws_doubles[0], lib.bbdm_groupnorm_bwd_workspace_doubles(N, x.C, G))
-            film = None if film_off is None else _TensorRef(self.film, 4 * film_off)
-            dfilm = None if film_off is None else _TensorRef(self.dfilm, 4 * film_off)
-            self._bop("bbdm_groupnorm_bwd_f32", x, x.ld, sstat(slot), self._pref(gn.weight), self._pref(gn.bias), film,
-                      self.film_total, da, da.ld, dadd, dadd.ld if dadd is not None else 0, dx, dx.ld, acc,
-                      gref(gn.weight), gref(gn.bias), dfilm, self.film_total, self._ws_d2, N, x.H, x.W, x.C, G,
-                      float(gn.eps), silu, rs)
-
+        self._gbufs: Dict[int, _Buf] = {}
+        self._written = set()
+        self._ws_need = {"_ws_f": 1, "_ws_f_side": 1, "_ws_d": 1, "_ws_d2": 1}
+        self._side_chains: List[tuple] = []
         f32 = dict(dtype=torch.float32, device=dev)
         self.dfilm = torch.zeros(N, self.film_total, **f32)
         self.dconvs: List[_PackedConv] = []
         self._padded_wgrads: List[tuple] = []
-        self._ws_f = _LateTensor()
+        self._ws_f, self._ws_f_floats = _LateTensor(), _LateInt()
         self._ws_f_side, self._ws_f_side_floats = _LateTensor(), _LateInt()
         self._bside_ranges: List[tuple] = []        # (first op, end op, joining op) of gradient-plan launches on the second stream
-        self._ws_f_floats = _LateInt()
-        self._ws_d = _LateTensor()
-        self._ws_d2 = _LateTensor()
+        self._ws_d, self._ws_d2 = _LateTensor(), _LateTensor()
         self.dout_nchw = torch.empty_like(self.out_nchw)
         self.need_input_grad = False
         self.dctx_tokens: Optional[_View] = None    # d context through the cross-attention keys / values (SpatialTransformer)
 
         rec_ends = []       # len(self.bops) after each tape record, in backward order
-        for rec in reversed(self.tape):
-            kind = rec[0]
-            if kind == "head":
-                _, seq, h, a, slot = rec
-                cpad = _round4(m.out_channels)
-                dy = self._tmp("DOUT", N, a.H, a.W, cpad)
-                self._bop("bbdm_nchw_to_nhwc_f32", _TensorRef(self.dout_nchw), m.out_channels, None, 0, dy, dy.ld, cpad,
-                          N, a.H, a.W)
-                dyv = _View(dy.buf, 0, dy.ld, N, a.H, a.W, cpad)
-                da = conv_bwd(seq[2], a, dyv, True, "DA")
-                dh = gview(h)
-                gn_bwd(seq[0], h, slot, None, da, None, 1, 0, dh, first_write(h))
-            elif kind == "res":
-                _, rb, x, a, xr, h1, a2, out, s1, s2, rs = rec
-                dout = gview(out)
-                bside = None
-                # dOut is read by the skip projection's and by the out conv's gradients: its maximum is measured once, on the main stream
-                dref = self._dy_bound(dout) if (self._h2_on(2) and dout.C % 4 == 0 and dout.ld % 4 == 0) else None
-                if isinstance(rb.skip_connection, nn.Conv2d):
-                    # the projection's gradients read only dOut (complete before this block's backward starts) and the block input: on the
-                    # second stream beside the block's own chain; joined before the launch that adds dXr (the last GroupNorm backward)
-                    # (only where the data gradient takes the bf16x3 GEMM -- conv_bwd's rule: the direct kernel owns a shared workspace)
-                    px = N * xr.H * xr.W
-                    sb = (rs == 0 and self._side_band(px, xr.C, rb.out_channels) and bool(m.gemm_bf3)
-                          and rb.skip_connection.weight.shape[1] == xr.C and bool(lib.bbdm_gemm_bf3_supported(px, dout.C, xr.C))
-                          and (px // 256) * -(-xr.C // 128) >= m.bf3_min_tiles)
-                    k0 = len(self.bops)
-                    dxr = conv_bwd(rb.skip_connection, xr, dout, True, "DXR", side=sb, dy_bound=dref)
-                    # (checked, not assumed -- and not an assert, which python -O drops: only the workspace-free pair may leave the main
-                    # stream; if conv_bwd ever chooses other kernels than the rule above predicts, the launches simply stay in order)
-                    if sb and [str(n) for n, _ in self.bops[k0:]] == ["bbdm_conv_wgrad_f32", "bbdm_conv1x1_bf3_f32"]:
-                        bside = (k0, len(self.bops))
-                else:
-                    dxr = dout
-                side_chains.clear()
-                da2 = conv_bwd(rb.out_layers[3], a2, dout, True, "DA2", side_chain=True, dy_bound=dref)
-                dh1 = self._tmp("DH1", N, h1.H, h1.W, h1.C)
-                if rb.use_scale_shift_norm:
-                    gn_bwd(rb.out_layers[0], h1, s2, self.film_off[id(rb)], da2, None, 1, 0, dh1, 0)
-                else:           # d emb_out[n, c] = sum_hw d(h + emb_out)
-                    gn_bwd(rb.out_layers[0], h1, s2, None, da2, None, 1, 0, dh1, 0)
-                    colsum_c[0] = max(colsum_c[0], 4 * N * h1.C)        # limb cells (csrc/stats_acc.h): 4 words per sum
-                    self._bop("bbdm_colsum_batched_f32", dh1, dh1.ld, self._ws_d,
-                              _TensorRef(self.dfilm, 4 * self.film_off[id(rb)]), self.film_total, N, h1.H * h1.W, h1.C)
-                da = conv_bwd(rb.in_layers[2], a, dh1, True, "DA", side_chain=True)
-                dx = gview(x)
-                for k0, k1 in ([bside] if bside is not None else []) + side_chains:
-                    self._bside_ranges.append((k0, k1, len(self.bops)))
-                side_chains.clear()
-                gn_bwd(rb.in_layers[0], x, s1, None, da, dxr, 1, rs, dx, first_write(x))
-            elif kind == "attn":
-                _, ab, x, a, qkv, at, lse, out, s0 = rec
-                T, C = x.H * x.W, x.C
-                dout = gview(out)
-                dat = conv_bwd(ab.proj_out, at, dout, True, "DAT")
-                dqkv = self._tmp("DQKV", N, x.H, x.W, 3 * C)
-                dwork = _TensorRef(torch.empty(N * ab.num_heads * T, **f32))
-                self._bop("bbdm_attention_bwd_f32", qkv, qkv.ld, at, at.ld, dat, dat.ld, lse, dwork, dqkv, dqkv.ld, N, T,
-                          ab.num_heads, C // ab.num_heads, 1 if ab.use_new_attention_order else 0)
-                da = conv_bwd(ab.qkv, a, dqkv, True, "DA")
-                dx = gview(x)
-                gn_bwd(ab.norm, x, s0, None, da, dout, 0, 0, dx, first_write(x))
-            elif kind == "st":
-                # SpatialTransformer (attention.py:249-263) in reverse; BasicTransformerBlock._forward (attention.py:215-218):
-                # x = attn1(norm1(x)) + x;  x = attn2(norm2(x), context) + x;  x = ff(norm3(x)) + x
-                _, st, x, a, s0, blocks, h_last, out, ctx = rec
-                heads, dh_ch = st.n_heads, st.d_head
-                inner = heads * dh_ch
-                H, W = x.H, x.W
-                rows = N * H * W
-                dout = gview(out)
-                ring = ["ST_DHA", "ST_DHB", "ST_DHC"]                      # gradient of the residual stream: three live at most
-                turn = [0]
-
-                def next_dh():
-                    turn[0] = (turn[0] + 1) % 3
-                    return self._tmp(ring[turn[0]], N, H, W, inner)
-
-                def accumulate(src: _View, dst: _View, acc: int):
-                    self._bop("bbdm_groupnorm_bwd_f32", None, 0, None, None, None, None, 0, None, 0, src, src.ld, dst, dst.ld,
-                              acc, None, None, None, 0, None, src.N, src.H, src.W, src.C, 1, 0.0, 0, 0)
-
-                def ln_bwd(ln_mod, xin: _View, dy: _View, dadd: _View) -> _View:
-                    ws_doubles[0] = max(ws_doubles[0], 8 * xin.C)      # [2][C] limb cells of 4 words
-                    dxv = next_dh()
-                    self._bop("bbdm_layernorm_bwd_f32", xin, xin.ld, self._pref(ln_mod.weight), dy, dy.ld, dadd, dadd.ld, dxv,
-                              dxv.ld, gref(ln_mod.weight), gref(ln_mod.bias), self._ws_d2, rows, xin.C, float(ln_mod.eps))
-                    return dxv
-
-                def attn_bwd(arec, dres: _View) -> _View:
-                    """dres = gradient of (to_out(attention) + residual); returns the gradient of the LayerNorm output."""
-                    att, xin, kv_src, q, kview, vview, at, lse = arec
-                    Tk = kv_src.H * kv_src.W
-                    dat = conv_bwd(att.to_out[0], at, dres, True, "ST_DAT")
-                    dq = self._tmp("ST_DQ", N, H, W, inner)
-                    dkv = self._tmp("ST_DKV", kv_src.N, kv_src.H, kv_src.W, 2 * inner)
-                    dk = _View(dkv.buf, 0, dkv.ld, kv_src.N, kv_src.H, kv_src.W, inner)
-                    dv = _View(dkv.buf, inner, dkv.ld, kv_src.N, kv_src.H, kv_src.W, inner)
-                    dwork = _TensorRef(torch.empty(N * heads * H * W, **f32))
-                    self._bop("bbdm_cross_attention_bwd_f32", q, q.ld, kview, vview, kview.ld, at, at.ld, dat, dat.ld, lse, dwork,
-                              dq, dq.ld, dk, dv, dkv.ld, N, H * W, Tk, heads, dh_ch)
-                    dln = conv_bwd(att.to_q, xin, dq, True, "ST_DLN")
-                    dsk = conv_bwd(att.to_k, kv_src, dk, True, "ST_DSK")
-                    dsv = conv_bwd(att.to_v, kv_src, dv, True, "ST_DSV")
-                    if kv_src is ctx:                       # context tokens: their gradient leaves through the UNet's d input
-                        if self.dctx_tokens is None:
-                            self.dctx_tokens = self._new(ctx.N, ctx.H, ctx.W, ctx.C)
-                            accumulate(dsk, self.dctx_tokens, 0)
-                        else:
-                            accumulate(dsk, self.dctx_tokens, 1)
-                        accumulate(dsv, self.dctx_tokens, 1)
-                    else:                                   # self-attention: keys and values come from the same LayerNorm output
-                        accumulate(dsk, dln, 1)
-                        accumulate(dsv, dln, 1)
-                    return dln
-
-                dh = conv_bwd(st.proj_out, h_last, dout, True, ring[0])
-                for blk, h_in, rec1, h1, rec2, h2, ln3, pr, gl in reversed(blocks):
-                    ff = blk.ff
-                    dgl = conv_bwd(ff.net[2], gl, dh, True, "ST_DGL")
-                    dpr = self._tmp("ST_DPR", N, H, W, pr.C)
-                    self._bop("bbdm_geglu_bwd_f32", pr, pr.ld, dgl, dgl.ld, dpr, dpr.ld, rows, gl.C)
-                    dln3 = conv_bwd(ff.net[0].proj, ln3, dpr, True, "ST_DLN")
-                    dh2 = ln_bwd(blk.norm3, h2, dln3, dh)
-                    dln2 = attn_bwd(rec2, dh2)
-                    dh1 = ln_bwd(blk.norm2, h1, dln2, dh2)
-                    dln1 = attn_bwd(rec1, dh1)
-                    dh = ln_bwd(blk.norm1, h_in, dln1, dh1)
-                da = conv_bwd(st.proj_in, a, dh, True, "DA")
-                dx = gview(x)
-                gn_bwd(st.norm, x, s0, None, da, dout, 0, 0, dx, first_write(x))
-            elif kind == "down":
-                _, ds, x, out = rec
-                dout = gview(out)
-                dx = gview(x)
-                if ds.use_conv:
-                    dfull = self._tmp("DDSF", N, x.H, x.W, ds.out_channels)
-                    self._bop("bbdm_groupnorm_bwd_f32", None, 0, None, None, None, None, 0, None, 0, dout, dout.ld, dfull,
-                              dfull.ld, 0, None, None, None, 0, None, N, x.H, x.W, dfull.C, 1, 0.0, 0, 3)
-                    dxs = conv_bwd(ds.op, x, dfull, True, "DA")
-                    self._bop("bbdm_groupnorm_bwd_f32", None, 0, None, None, None, None, 0, None, 0, dxs, dxs.ld, dx, dx.ld,
-                              first_write(x), None, None, None, 0, None, N, x.H, x.W, x.C, 1, 0.0, 0, 0)
-                else:
-                    self._bop("bbdm_groupnorm_bwd_f32", None, 0, None, None, None, None, 0, None, 0, dout, dout.ld, dx, dx.ld,
-                              first_write(x), None, None, None, 0, None, N, x.H, x.W, x.C, 1, 0.0, 0, 1)
-            elif kind == "up":
-                _, us, x, u, out = rec
-                dout = gview(out)
-                dx = gview(x)
-                du = conv_bwd(us.conv, u, dout, True, "DA") if us.use_conv else dout
-                self._bop("bbdm_groupnorm_bwd_f32", None, 0, None, None, None, None, 0, None, 0, du, du.ld, dx, dx.ld,
-                          first_write(x), None, None, None, 0, None, N, x.H, x.W, x.C, 1, 0.0, 0, 2)
-            elif kind == "stem":
-                _, conv, x, out = rec
-                dout = gview(out)
-                conv_bwd(conv, x, dout, False, "DX0")
-                # d input (only when x / context require grad, e.g. a trainable SpatialRescaler context): own op list
-                main, self.bops = self.bops, []
-                pk = _PackedConv(conv.weight, None, dout.C, dgrad=True)
-                self.dconvs.append(pk)
-                self.dx0 = self._tmp("DX0", N, x.H, x.W, x.C)
-                self._bop("bbdm_conv2d_nhwc_f32", dout, dout.ld, _TensorRef(pk.packed), None, None, 0, self.dx0,
-                          self.dx0.ld, 0, None, 0, None, None, 0, 0, N, x.H, x.W, dout.C, x.C, 3)
-                self.bops_x0, self.bops = self.bops, main
+        for kind, *rec in reversed(self.tape):
+            getattr(self, "_bwd_" + kind)(*rec)         # (_bwd_head, _res, _attn, _st, _down, _up, _stem: the kinds of _record_params)
             rec_ends.append(len(self.bops))
         self._segment_backward(rec_ends)
-        self._ws_f.t = torch.empty(ws_floats[0], **f32)
-        self._ws_f_floats.v = ws_floats[0]
-        self._ws_f_side.t = torch.empty(ws_side_floats[0], **f32)
-        self._ws_f_side_floats.v = ws_side_floats[0]
-        self._ws_d.t = torch.empty(colsum_c[0], dtype=torch.float64, device=dev)
-        self._ws_d2.t = torch.empty(ws_doubles[0], dtype=torch.float64, device=dev)
+        for ws, n in self._ws_need.items():
+            getattr(self, ws).t = torch.empty(n, dtype=torch.float64 if ws.startswith("_ws_d") else torch.float32, device=dev)
+        self._ws_f_floats.v, self._ws_f_side_floats.v = self._ws_need["_ws_f"], self._ws_need["_ws_f_side"]
         # embedding-path backward scratch
         ted = 4 * m.model_channels
         self.d_emb = torch.empty(N, ted, **f32)
@@ -2065,26 +2070,19 @@ class _Plan:
 
     @staticmethod
     def _record_params(rec):
-        kind = rec[0]
-        mods = []
+        kind, mod = rec[0], rec[1]
         if kind == "head":
-            mods = [rec[1][0], rec[1][2]]
+            mods = [mod[0], mod[2]]
         elif kind == "res":
-            rb = rec[1]
-            mods = [rb.in_layers[0], rb.in_layers[2], rb.out_layers[0], rb.out_layers[3]]
-            if isinstance(rb.skip_connection, nn.Conv2d):
-                mods.append(rb.skip_connection)
+            mods = [mod.in_layers[0], mod.in_layers[2], mod.out_layers[0], mod.out_layers[3]]
+            if isinstance(mod.skip_connection, nn.Conv2d):
+                mods.append(mod.skip_connection)
         elif kind == "attn":
-            ab = rec[1]
-            mods = [ab.norm, ab.qkv, ab.proj_out]
-        elif kind == "st":
-            mods = [rec[1]]
-        elif kind == "down":
-            mods = [rec[1].op] if rec[1].use_conv else []
-        elif kind == "up":
-            mods = [rec[1].conv] if rec[1].use_conv else []
-        elif kind == "stem":
-            mods = [rec[1]]
+            mods = [mod.norm, mod.qkv, mod.proj_out]
+        elif kind in ("down", "up"):
+            mods = [mod.op if kind == "down" else mod.conv] if mod.use_conv else []
+        else:               # "st", "stem": the module's own parameters
+            mods = [mod]
         return [p for mod in mods for p in mod.parameters()]
 
     def _segment_backward(self, rec_ends):
