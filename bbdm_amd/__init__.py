@@ -7,7 +7,9 @@ from .model import BrownianBridgeModel, LatentBrownianBridgeModel, bridge_schedu
 from .unet import UNetModel  # noqa: F401
 from .cond_stage import SpatialRescaler  # noqa: F401
 from .sampler import BridgeSampler, SamplingParams  # noqa: F401
+from .latent_cache import CachedPairs, LatentCache  # noqa: F401
 from .optim import EMA, FusedAdam, FusedRMSprop, FusedSGD, get_optimizer  # noqa: F401
 
 __all__ = ["BrownianBridgeModel", "LatentBrownianBridgeModel", "UNetModel", "SpatialRescaler", "bridge_schedule",
-           "BridgeSampler", "SamplingParams", "philox_normal", "FusedAdam", "FusedSGD", "FusedRMSprop", "EMA", "get_optimizer"]
+           "BridgeSampler", "SamplingParams", "philox_normal", "FusedAdam", "FusedSGD", "FusedRMSprop", "EMA", "get_optimizer",
+           "LatentCache", "CachedPairs"]

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBDM_HIP_LIB overrides the library path (A/B runs of kernel variants); the default is the in-tree build
 LIB_PATH = os.environ.get("BBDM_HIP_LIB") or os.path.join(_HERE, "libbbdm_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _P = c_void_p
 # name -> (restype, argtypes); must list every symbol of include/bbdm_hip.h (tests/test_abi.py checks it)
@@ -92,6 +92,12 @@ SIGNATURES = {
     "bbdm_bb_p_sample_step_philox_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int, c_int,
                                                  _P, _P, _P, c_int, c_int, _P]),
     "bbdm_bb_q_sample_philox_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    # latent cache (ABI 31; bbdm_amd/latent_cache.py): q_sample over gathered cache rows, per-channel statistics of a cache tensor
+    "bbdm_bb_q_sample_cached_f32": (c_int, [_P, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P,
+                                            c_int, c_int, c_int, _P]),
+    "bbdm_bb_q_sample_cached_philox_f32": (c_int, [_P, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P,
+                                                   _P, _P, _P, c_int, c_int, c_int, _P]),
+    "bbdm_latent_channel_stats_f32": (c_int, [_P, ctypes.c_longlong, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
     "bbdm_bb_predict_x0_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "bbdm_bb_loss_f32": (c_int, [_P, _P, _P, _P, c_size_t, c_int, _P]),
     "bbdm_gemm_packed_b_floats": (c_size_t, [c_int, c_int]),

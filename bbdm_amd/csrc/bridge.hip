@@ -306,6 +306,129 @@ __global__ void __launch_bounds__(256) q_sample_philox_kernel(const float* __res
     }
 }
 
+// ---- latent cache (bbdm_amd/latent_cache.py): q_sample whose x0 / y rows are GATHERED from two cache tensors of raw (un-normalised)
+// latents, one image per blockIdx.y as above.  Replaces the two frozen-encoder passes of LatentBrownianBridgeModel.forward
+// (LatentBrownianBridgeModel.py:68-72) and encode()'s normalisation (:92-97) in front of q_sample (BrownianBridgeModel.py:128-146).
+// NORM: (z - mean[c]) / std[c], two separate fp32 operations with an IEEE division -- the operations torch performs for encode(); the
+// channel of element e is e / hw, so an unaligned group of four may straddle two channels.  The q_sample expressions are
+// q_sample_kernel's, in the same order.  An image whose index is outside [0, M) dereferences nothing and gets NaN in all three outputs.
+// PHILOX: the noise of domain 1 in registers (noise unused), else the noise tensor (seed / ordinal unused).
+template <bool VEC, bool PHILOX>
+__global__ void __launch_bounds__(256) q_sample_cached_kernel(const float* __restrict__ ori, const float* __restrict__ cond, int64_t M,
+                                                              const int64_t* __restrict__ idx_ori, const int64_t* __restrict__ idx_cond,
+                                                              const float* __restrict__ ori_mean, const float* __restrict__ ori_std,
+                                                              const float* __restrict__ cond_mean, const float* __restrict__ cond_std,
+                                                              int hw, const float* __restrict__ noise,
+                                                              const int64_t* __restrict__ seed_arr, const int64_t* __restrict__ ordinal_arr,
+                                                              const int64_t* __restrict__ t, const float* __restrict__ m_t,
+                                                              const float* __restrict__ var_t, float* __restrict__ x_t,
+                                                              float* __restrict__ target, float* __restrict__ y_out, int per_sample,
+                                                              int objective) {
+    const int n = blockIdx.y;
+    const int64_t io = idx_ori[n], ic = idx_cond[n];
+    const size_t base = (size_t)n * per_sample;
+    const unsigned groups = ((unsigned)per_sample + 3u) / 4u;
+    if (io < 0 || io >= M || ic < 0 || ic >= M) {
+        const float nan = __builtin_nanf("");
+        const float bad[4] = {nan, nan, nan, nan};
+        for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < groups; q += gridDim.x * 256u) {
+            const size_t i = base + 4 * (size_t)q;
+            const int count = per_sample - (int)(4u * q);
+            store_group<VEC>(x_t + i, count, bad);
+            store_group<VEC>(target + i, count, bad);
+            store_group<VEC>(y_out + i, count, bad);
+        }
+        return;
+    }
+    const float* __restrict__ a_row = ori + (size_t)io * per_sample;
+    const float* __restrict__ b_row = cond + (size_t)ic * per_sample;
+    const int64_t tt = t[n];
+    const float m = m_t[tt];
+    const float sig = sqrtf(var_t[tt]);
+    int64_t seed = 0, ordinal = 0;
+    if (PHILOX) seed = seed_arr[n], ordinal = ordinal_arr[n];
+    for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < groups; q += gridDim.x * 256u) {
+        const size_t k = 4 * (size_t)q;
+        const int count = per_sample - (int)(4u * q);
+        float av[4], bv[4], z[4], xv[4], tv[4];
+        load_group<VEC>(a_row + k, count, av);
+        load_group<VEC>(b_row + k, count, bv);
+        if (PHILOX) philox_normal4(seed, ordinal, BBDM_NOISE_Q_SAMPLE, q, z);
+        else load_group<VEC>(noise + base + k, count, z);
+        if (ori_mean) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < count) {                                   // (the tail's elements have no channel)
+                    const int c = (int)((4u * q + (unsigned)j) / (unsigned)hw);
+                    av[j] = (av[j] - ori_mean[c]) / ori_std[c];
+                    bv[j] = (bv[j] - cond_mean[c]) / cond_std[c];
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a = av[j], b = bv[j], e = z[j];
+            float tg;
+            if (objective == 0) tg = m * (b - a) + sig * e;
+            else if (objective == 1) tg = e;
+            else tg = b - a;
+            xv[j] = (1.f - m) * a + m * b + sig * e;
+            tv[j] = tg;
+        }
+        store_group<VEC>(x_t + base + k, count, xv);
+        store_group<VEC>(target + base + k, count, tv);
+        store_group<VEC>(y_out + base + k, count, bv);
+    }
+}
+
+// Per-channel sums over all M rows of one cache tensor [M, C, hw] -- the mean / variance loops of BBDMRunner.get_latent_mean_std
+// (BBDMRunner.py:85-162).  SQ = false: sum of z into cells[c]; SQ = true: sum of (z - mean_f32[c])^2 into cells[C + c], mean_f32 re-derived
+// from cells[c] by every block (the first launch has finished: same stream).  One (row, channel) plane per block iteration: every thread
+// sums its groups of four in fp64 in a fixed order, the block reduces in a fixed tree, and the plane's partial goes into the exact limb
+// cell (stats_acc.h).  The partial is a function of the plane's values alone (the same tree with 128-bit and with element accesses, the
+// block size is fixed) and the limbs add associatively, so the sums are a function of the MULTISET of rows: not of their order, and not
+// of how many blocks share them.  A non-finite partial bumps the cell's fourth word: that channel reads NaN.
+template <bool VEC, bool SQ>
+__global__ void __launch_bounds__(256) latent_stats_kernel(const float* __restrict__ z, int64_t M, int C, int hw,
+                                                           unsigned long long* __restrict__ cells, double count) {
+    __shared__ double red[4];
+    const int c = blockIdx.y;
+    double mean = 0.0;
+    if (SQ) mean = (double)(float)(sa_load(cells + (size_t)c * SA_W) / count);
+    unsigned long long* cell = cells + ((size_t)(SQ ? C : 0) + c) * SA_W;
+    const int groups = (hw + 3) / 4;
+    for (int64_t r = blockIdx.x; r < M; r += gridDim.x) {
+        const float* __restrict__ p = z + ((size_t)r * C + c) * hw;
+        double s = 0.0;
+        for (int q = threadIdx.x; q < groups; q += 256) {
+            const int cnt = hw - 4 * q;
+            float v[4];
+            load_group<VEC>(p + 4 * (size_t)q, cnt, v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < cnt) {
+                    const double d = (double)v[j] - mean;
+                    s += SQ ? d * d : d;
+                }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) sa_add(cell, (red[0] + red[1]) + (red[2] + red[3]));
+        __syncthreads();                                   // red is rewritten by the next row
+    }
+}
+
+__global__ void latent_stats_final_kernel(const unsigned long long* __restrict__ cells, int C, double count, float* __restrict__ mean,
+                                          float* __restrict__ var, float* __restrict__ stdev) {
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) {
+        const double v = sa_load(cells + ((size_t)C + c) * SA_W) / count;
+        mean[c] = (float)(sa_load(cells + (size_t)c * SA_W) / count);
+        var[c] = (float)v;
+        stdev[c] = (float)sqrt(v);
+    }
+}
+
 __global__ void __launch_bounds__(256) loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            unsigned long long* __restrict__ partial, size_t count, int loss_type) {
     __shared__ double red[4];
@@ -410,6 +533,36 @@ int launch_p_step_philox(const char* what, const float* x_t, const float* y, con
     else
         hipLaunchKernelGGL((p_step_philox_kernel<false, P>), grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal,
                            m_t, variance_t, t, t_next, flag, params, objective, x_next, x0_recon, x_next_alias, per_sample);
+    BBDM_CHECK_LAUNCH(what);
+    return BBDM_OK;
+}
+
+// The checks and the launch shared by the two cached q_sample entry points (PHILOX as in the kernel).
+template <bool PHILOX>
+int launch_q_sample_cached(const char* what, const float* ori, const float* cond, long long M, const int64_t* idx_ori,
+                           const int64_t* idx_cond, const float* ori_mean, const float* ori_std, const float* cond_mean,
+                           const float* cond_std, int hw, const float* noise, const int64_t* seed, const int64_t* ordinal,
+                           const int64_t* t, const float* m_t, const float* variance_t, float* x_t, float* target, float* y_out, int N,
+                           int per_sample, int objective, void* stream) {
+    BBDM_REQUIRE(ori && cond && idx_ori && idx_cond && t && m_t && variance_t && x_t && target && y_out, "%s: null pointer", what);
+    BBDM_REQUIRE(PHILOX ? (seed && ordinal) : noise != nullptr, "%s: null noise source", what);
+    const int stats = (ori_mean != nullptr) + (ori_std != nullptr) + (cond_mean != nullptr) + (cond_std != nullptr);
+    BBDM_REQUIRE(stats == 0 || stats == 4, "%s: pass all four of ori_mean / ori_std / cond_mean / cond_std or none", what);
+    BBDM_REQUIRE(M > 0 && N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "%s: bad args", what);
+    BBDM_REQUIRE(hw > 0 && per_sample % hw == 0, "%s: per_sample must be a multiple of hw", what);
+    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32), "%s: per_sample / 4 must fit the 32-bit counter word", what);
+    const dim3 grid = group_grid(N, per_sample);
+    // (per_sample % 4 == 0 makes every gathered row as aligned as its tensor)
+    const bool vec = per_sample % 4 == 0 && aligned16(ori) && aligned16(cond) && aligned16(noise) && aligned16(x_t) &&
+                     aligned16(target) && aligned16(y_out);
+    if (vec)
+        hipLaunchKernelGGL((q_sample_cached_kernel<true, PHILOX>), grid, dim3(256), 0, (hipStream_t)stream, ori, cond, (int64_t)M,
+                           idx_ori, idx_cond, ori_mean, ori_std, cond_mean, cond_std, hw, noise, seed, ordinal, t, m_t, variance_t,
+                           x_t, target, y_out, per_sample, objective);
+    else
+        hipLaunchKernelGGL((q_sample_cached_kernel<false, PHILOX>), grid, dim3(256), 0, (hipStream_t)stream, ori, cond, (int64_t)M,
+                           idx_ori, idx_cond, ori_mean, ori_std, cond_mean, cond_std, hw, noise, seed, ordinal, t, m_t, variance_t,
+                           x_t, target, y_out, per_sample, objective);
     BBDM_CHECK_LAUNCH(what);
     return BBDM_OK;
 }
@@ -532,6 +685,49 @@ extern "C" int bbdm_bb_q_sample_philox_f32(const float* x0, const float* y, cons
         hipLaunchKernelGGL(q_sample_philox_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x0, y, seed, ordinal, t, m_t,
                            variance_t, x_t, target, per_sample, objective);
     BBDM_CHECK_LAUNCH("q_sample_philox");
+    return BBDM_OK;
+}
+
+extern "C" int bbdm_bb_q_sample_cached_f32(const float* ori, const float* cond, long long M, const int64_t* idx_ori,
+                                           const int64_t* idx_cond, const float* ori_mean, const float* ori_std,
+                                           const float* cond_mean, const float* cond_std, int hw, const float* noise,
+                                           const int64_t* t, const float* m_t, const float* variance_t, float* x_t, float* target,
+                                           float* y_out, int N, int per_sample, int objective, void* stream) {
+    return launch_q_sample_cached<false>("q_sample_cached", ori, cond, M, idx_ori, idx_cond, ori_mean, ori_std, cond_mean, cond_std,
+                                         hw, noise, nullptr, nullptr, t, m_t, variance_t, x_t, target, y_out, N, per_sample, objective,
+                                         stream);
+}
+
+extern "C" int bbdm_bb_q_sample_cached_philox_f32(const float* ori, const float* cond, long long M, const int64_t* idx_ori,
+                                                  const int64_t* idx_cond, const float* ori_mean, const float* ori_std,
+                                                  const float* cond_mean, const float* cond_std, int hw, const int64_t* seed,
+                                                  const int64_t* ordinal, const int64_t* t, const float* m_t,
+                                                  const float* variance_t, float* x_t, float* target, float* y_out, int N,
+                                                  int per_sample, int objective, void* stream) {
+    return launch_q_sample_cached<true>("q_sample_cached_philox", ori, cond, M, idx_ori, idx_cond, ori_mean, ori_std, cond_mean,
+                                        cond_std, hw, nullptr, seed, ordinal, t, m_t, variance_t, x_t, target, y_out, N, per_sample,
+                                        objective, stream);
+}
+
+extern "C" int bbdm_latent_channel_stats_f32(const float* z, long long M, int C, int hw, double* cells, float* mean, float* var,
+                                             float* stdev, int row_blocks, void* stream) {
+    BBDM_REQUIRE(z && cells && mean && var && stdev, "latent_channel_stats: null pointer");
+    // one sa_add per (row, channel) and pass: a limb has 23 spare bits (stats_acc.h)
+    BBDM_REQUIRE(M > 0 && M < (1ll << 23) && C > 0 && C <= 65535 && hw > 0 && row_blocks >= 0, "latent_channel_stats: bad args");
+    unsigned long long* cell = reinterpret_cast<unsigned long long*>(cells);     // [2][C] cells of 4 x 8 bytes, zeroed by the caller
+    const long long want = row_blocks ? row_blocks : 1024;
+    const dim3 grid((unsigned)(want < M ? want : M), (unsigned)C);
+    const double count = (double)M * (double)hw;
+    if (hw % 4 == 0 && aligned16(z)) {
+        hipLaunchKernelGGL((latent_stats_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
+        hipLaunchKernelGGL((latent_stats_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
+    } else {
+        hipLaunchKernelGGL((latent_stats_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
+        hipLaunchKernelGGL((latent_stats_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
+    }
+    hipLaunchKernelGGL(latent_stats_final_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cell, C, count,
+                       mean, var, stdev);
+    BBDM_CHECK_LAUNCH("latent_channel_stats");
     return BBDM_OK;
 }
 

@@ -201,6 +201,10 @@ class BrownianBridgeModel(nn.Module):
         if seeds is None:
             noise = torch.randn_like(x0) if noise is None else noise
         x_t, objective = self.q_sample(x0, y, t, noise, seeds=seeds, ordinals=ordinals)
+        return self._denoise_and_loss(x_t, objective, y, context, t)
+
+    def _denoise_and_loss(self, x_t, objective, y, context, t):
+        """BrownianBridgeModel.py:107-126: everything of p_losses after q_sample."""
         objective_recon = self.denoise_fn(x_t, timesteps=t, context=context)
         if objective_recon.requires_grad:
             from .autograd import bb_loss      # differentiable HIP loss (training path)
@@ -420,7 +424,91 @@ class LatentBrownianBridgeModel(BrownianBridgeModel):
             self.cond_stage_model.apply(weights_init)
         return self
 
+    # ---- latent cache (bbdm_amd/latent_cache.py) -------------------------------------------------------
+    _latent_cache = None
+
+    def attach_latent_cache(self, cache):
+        """From here on ``forward`` accepts int64 index tensors [N] in place of the two image batches and reads the latents from
+        ``cache`` (a :class:`bbdm_amd.latent_cache.LatentCache`) instead of running the frozen encoder.  Image inputs keep their
+        path.  The cache holds no context, so the model must be ``nocond`` (LatentCache.build refuses the others too)."""
+        if self.cond_stage_model is not None:
+            raise ValueError(f"a latent cache cannot serve condition_key {self.condition_key!r}: its context is computed from the pixels")
+        if tuple(cache.ori.shape) != tuple(cache.cond.shape) or cache.ori.dim() != 4:
+            raise ValueError(f"latent cache tensors must be two equal [M, C, h, w], got {tuple(cache.ori.shape)} / {tuple(cache.cond.shape)}")
+        _need_gpu(cache.ori, cache.cond)
+        self._latent_cache = cache
+
+    def detach_latent_cache(self):
+        self._latent_cache = None
+
+    def _cache_indices(self, idx, M, device, what):
+        """int64 [N] on the device.  Indices that arrive on the CPU are range-checked here; indices already on the device are not read
+        back (no sync): the kernel answers an out-of-range one with NaN rows for that image -- see ``skip_nonfinite`` in
+        bbdm_amd/optim.py, which then skips the step."""
+        if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= M):
+            raise IndexError(f"{what}: index out of range for a latent cache of {M} rows")
+        return idx.to(device=device, dtype=torch.int64).contiguous()
+
+    def _forward_cached(self, idx_ori, idx_cond):
+        if idx_ori.dim() != 1 or tuple(idx_cond.shape) != tuple(idx_ori.shape) or torch.is_floating_point(idx_cond):
+            raise ValueError(f"latent-cache indices must be two integer tensors [N], got {tuple(idx_ori.shape)} {idx_ori.dtype} / "
+                             f"{tuple(idx_cond.shape)} {idx_cond.dtype}")
+        cache = self._latent_cache
+        if cache is None:
+            raise RuntimeError("integer inputs are rows of a latent cache, and none is attached (attach_latent_cache)")
+        h, w, img_size = cache.ori.shape[2], cache.ori.shape[3], self.image_size
+        assert h == img_size and w == img_size, f'height and width of image must be {img_size}'
+        # the same call as BrownianBridgeModel.forward: the generator advances identically on both paths
+        t = torch.randint(0, self.num_timesteps, (idx_ori.shape[0],), device=cache.ori.device).long()
+        return self.p_losses_cached(idx_ori, idx_cond, t)
+
+    def p_losses_cached(self, idx_ori, idx_cond, t, noise=None, seeds=None, ordinals=None):
+        """``p_losses`` on rows of the attached cache: one gather + normalise + q_sample kernel, then the UNet, the loss and x0_recon
+        as in ``p_losses``.  ``noise`` / ``seeds`` / ``ordinals`` as there; no encoder launch happens here."""
+        if self.loss_type not in _LOSSES:
+            raise NotImplementedError()
+        if self.objective not in _OBJECTIVES:
+            raise NotImplementedError()
+        cache = self._latent_cache
+        if cache is None:
+            raise RuntimeError("no latent cache attached (attach_latent_cache)")
+        ori, cond = cache.ori, cache.cond
+        M, C, hw, dev = ori.shape[0], ori.shape[1], ori.shape[2] * ori.shape[3], ori.device
+        io = self._cache_indices(idx_ori, M, dev, "idx_ori")
+        ic = self._cache_indices(idx_cond, M, dev, "idx_cond")
+        n = io.shape[0]
+        if ic.shape[0] != n:
+            raise ValueError(f"idx_cond: {ic.shape[0]} indices for {n} images")
+        if seeds is not None and noise is not None:
+            raise ValueError("p_losses_cached: pass noise or seeds, not both")
+        if seeds is None and ordinals is not None:
+            raise ValueError("p_losses_cached: ordinals without seeds")
+        stats = [None] * 4
+        if self.model_config.normalize_latent:              # read at call time, like encode()
+            stats = [_f32c(v.to(dev).reshape(-1)) for v in self._latent_stats(False) + self._latent_stats(True)]
+            if any(v.numel() != C for v in stats):
+                raise ValueError(f"latent mean / std must have {C} channels")
+        tc = t.to(torch.int64).contiguous()
+        _need_gpu(ori, cond, tc)
+        x_t, target, y = (torch.empty((n,) + tuple(ori.shape[1:]), dtype=torch.float32, device=dev) for _ in range(3))
+        head = (ori.data_ptr(), cond.data_ptr(), M, io.data_ptr(), ic.data_ptr(), *(None if v is None else v.data_ptr() for v in stats), hw)
+        tail = (tc.data_ptr(), self.m_t.data_ptr(), self.variance_t.data_ptr(), x_t.data_ptr(), target.data_ptr(), y.data_ptr(),
+                n, C * hw, _OBJECTIVES[self.objective])
+        if seeds is not None:
+            sd = _i64_per_image(seeds, n, dev, "seeds")
+            od = _i64_per_image(0 if ordinals is None else ordinals, n, dev, "ordinals")
+            _launch(ori, "bbdm_bb_q_sample_cached_philox_f32", *head, sd.data_ptr(), od.data_ptr(), *tail)
+        else:
+            noise = _f32c(torch.randn(x_t.shape, dtype=torch.float32, device=dev) if noise is None else noise)
+            _need_gpu(noise)
+            if tuple(noise.shape) != tuple(x_t.shape):
+                raise ValueError(f"noise must be {tuple(x_t.shape)}, got {tuple(noise.shape)}")
+            _launch(ori, "bbdm_bb_q_sample_cached_f32", *head, noise.data_ptr(), *tail)
+        return self._denoise_and_loss(x_t, target, y, None, tc)
+
     def forward(self, x, x_cond, context=None):
+        if not torch.is_floating_point(x):                  # rows of the attached latent cache instead of images
+            return self._forward_cached(x, x_cond)
         # both images go through the frozen encoder without a graph; only the UNet (+ rescaler) is trained
         with torch.no_grad():
             latents = [self.encode(img, cond=flag).detach() for img, flag in ((x, False), (x_cond, True))]

@@ -24,6 +24,10 @@ chunk tables and applied INSIDE the update pass (no scale pass over the gradient
 :func:`clip_grad_norm_` are the standalone forms (``torch.nn.utils.clip_grad_norm_``'s signature, norm type 2) for
 optimizers torch provides.  The norm is summed in a fixed order and accumulated in exact integer limbs
 (``csrc/stats_acc.h``): the same gradient values give the same bits on every run and on every rank.
+``skip_nonfinite`` is also what answers a bad row index on the latent-cache path (``LatentBrownianBridgeModel.forward(indices)``,
+bbdm_amd/latent_cache.py): indices that arrive on the CPU raise ``IndexError`` before any launch, but indices already on the
+device are not read back, the gather kernel fills that image's rows with NaN, the loss and every gradient become NaN, and the
+guard skips the step instead of writing them into the weights.
 """
 from __future__ import annotations
 

@@ -378,6 +378,39 @@ int bbdm_bb_p_sample_step_requests_philox_f32(const float* x_t, const float* y, 
 int bbdm_bb_q_sample_philox_f32(const float* x0, const float* y, const int64_t* seed, const int64_t* ordinal,
                                 const int64_t* t, const float* m_t, const float* variance_t, float* x_t, float* target,
                                 int N, int per_sample, int objective, void* stream);
+/* ---- latent cache (ABI 31; bbdm_amd/latent_cache.py) -------------------------------------------------
+ * bbdm_bb_q_sample_f32 whose x0 and y rows are gathered from two cache tensors of raw (un-normalised) first-stage latents:
+ * image n reads ori[idx_ori[n]] and cond[idx_cond[n]] (ori, cond: fp32 [M, per_sample]; idx_*: int64[N] on the device).
+ * Replaces the two frozen-encoder passes of LatentBrownianBridgeModel.forward (LatentBrownianBridgeModel.py:68-72) and the
+ * normalisation of encode() (:92-97) in front of q_sample (BrownianBridgeModel.py:128-146).  ori_mean / ori_std / cond_mean /
+ * cond_std: fp32 [C] with C = per_sample / hw, all four or all NULL; with them every element is (z - mean[c]) / std[c], c its
+ * flat index / hw, as two fp32 operations with a correctly rounded division (what torch evaluates).  The bridge arithmetic is
+ * bbdm_bb_q_sample_f32's, in the same order: the outputs equal that kernel fed the gathered (and normalised) rows bit for bit.
+ * y_out [N, per_sample] receives the (normalised) condition rows, the y of predict_x0_from_objective.  An index outside
+ * [0, M) is never dereferenced: that image's rows of x_t, target and y_out are filled with NaN, every other image is
+ * unaffected.  N <= 65535.  128-bit accesses when per_sample % 4 == 0 and the tensor pointers are 16-byte aligned. */
+int bbdm_bb_q_sample_cached_f32(const float* ori, const float* cond, long long M, const int64_t* idx_ori,
+                                const int64_t* idx_cond, const float* ori_mean, const float* ori_std, const float* cond_mean,
+                                const float* cond_std, int hw, const float* noise, const int64_t* t, const float* m_t,
+                                const float* variance_t, float* x_t, float* target, float* y_out, int N, int per_sample,
+                                int objective, void* stream);
+/* The same with the noise of bbdm_bb_q_sample_philox_f32 (domain 1, per-image seed / ordinal) generated in registers. */
+int bbdm_bb_q_sample_cached_philox_f32(const float* ori, const float* cond, long long M, const int64_t* idx_ori,
+                                       const int64_t* idx_cond, const float* ori_mean, const float* ori_std,
+                                       const float* cond_mean, const float* cond_std, int hw, const int64_t* seed,
+                                       const int64_t* ordinal, const int64_t* t, const float* m_t, const float* variance_t,
+                                       float* x_t, float* target, float* y_out, int N, int per_sample, int objective,
+                                       void* stream);
+/* Per-channel mean, population variance and its square root over all M rows of one cache tensor z [M, C, hw] -- the two
+ * walks of BBDMRunner.get_latent_mean_std (BBDMRunner.py:85-162; with drop_last and equal batches its mean of per-batch means
+ * and of per-batch mean squared deviations are these global ones).  Two passes on the stream: sums -> mean, rounded once to
+ * fp32; sums of (z - mean_f32)^2 -> var (fp32) and std = (float)sqrt of the fp64 variance.  The sums live in exact
+ * integer-limb cells (csrc/stats_acc.h); every (row, channel) plane contributes one fp64 partial that depends on the plane's
+ * values alone, so the results are a function of the multiset of rows: the same bits for any row order and any row_blocks
+ * (blocks sharing the rows; 0 = the default).  A non-finite value makes its channel's three outputs NaN.
+ * cells: 2 * C cells of 4 x 8 bytes, zeroed by the caller.  M < 2^23. */
+int bbdm_latent_channel_stats_f32(const float* z, long long M, int C, int hw, double* cells, float* mean, float* var,
+                                  float* stdev, int row_blocks, void* stream);
 /* predict_x0_from_objective alone (BBM.py:148-160), per-sample t (used by p_losses :121). */
 int bbdm_bb_predict_x0_f32(const float* x_t, const float* y, const float* pred, const int64_t* t,
                            const float* m_t, const float* variance_t, float* x0_recon,
