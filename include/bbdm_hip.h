@@ -776,6 +776,36 @@ int bbdm_rmsprop_ema_step_clip_f32(const BbdmOptChunk* table, int nchunks, doubl
 int bbdm_images_to_u8_f32(const float* x_nchw, unsigned char* out_nhwc, int N, int C, int H, int W, int to_normal,
                           void* stream);
 
+/* ---- evaluation metrics of a sample set (ABI 32; csrc/metrics.hip, bbdm_amd/metrics.py) ------------------------------------- */
+/* Replace the CPU loop of evaluation/diversity.py:8-39 (every PNG re-opened with PIL, the per-pixel standard deviation formed with
+ * torch on the host) and add the paired metrics the reference has none of, on the uint8 NHWC images bbdm_images_to_u8_f32 writes --
+ * the bytes of the PNG files, so a metric taken from device tensors equals the one taken from the files.  Every accumulator is
+ * DEVICE memory the CALLER owns and ZEROES; every result is a function of the input bytes alone (integer sums; fp values enter a
+ * csrc/stats_acc.h cell of 4 64-bit words as exact fixed-point limbs), whatever the grid, the tiles or the order of the workgroups.
+ *   bbdm_u8_pair_sums      : a, b [N][H][W][C] -> out[N][2] = (sum |a - b|, sum (a - b)^2) per image, exact integers.  Any H, W, C
+ *                            >= 1, any alignment (16-byte loads where a and b are congruent mod 16, 4-byte loads mod 4, else bytes);
+ *   bbdm_u8_ssim           : a, b [N][H][W][C], H, W >= 11 (smaller: BBDM_E_BADARG) -> cells[N][4] += the SSIM map of Wang et al.
+ *                            2004 summed over the C channels and the (H - 10) (W - 10) valid window positions.  `w`: the 11 window
+ *                            weights, HOST memory, read during the call; the 2-D window is w (x) w, applied as a horizontal and a
+ *                            vertical 11-tap pass, taps in index order, every step an fp64 fma.  Per channel, with E[.] = the window
+ *                            sum:  mx = E[x], my = E[y], sxx = E[x^2] - mx^2, syy = E[y^2] - my^2, sxy = E[x y] - mx my,
+ *                            map = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sxx + syy + C2)), C1 = (0.01 * 255)^2,
+ *                            C2 = (0.03 * 255)^2.  A map value enters the sum cut to a multiple of 2^-52;
+ *   bbdm_u8_ssim_read      : out[N] (fp64, device) = the accumulated sums (NaN for a cell that met a non-finite value);
+ *   bbdm_u8_diversity      : x [M][S][H][W][C], 1 <= S <= 65536 -> cells[M][4] += the sum over the H W C elements of the standard
+ *                            deviation over the S samples, in fp32 and in the order of diversity.py:26-35: v_j = float(u_j);
+ *                            mean = 0, mean += v_j (j = 0..S-1), mean /= S; var = 0, var += (v_j - mean) * (v_j - mean), var /= S;
+ *                            std = sqrt(var) (division and square root correctly rounded, no contraction).  S = 1, or equal
+ *                            samples: exactly 0.  The fp32 values are summed without rounding;
+ *   bbdm_u8_diversity_read : out[M] (fp64, device) = the accumulated sums; the caller divides by H W C. */
+int bbdm_u8_pair_sums(const unsigned char* a, const unsigned char* b, unsigned long long* out, int N, int H, int W, int C,
+                      void* stream);
+int bbdm_u8_ssim(const unsigned char* a, const unsigned char* b, const double* w, unsigned long long* cells, int N, int H, int W,
+                 int C, void* stream);
+int bbdm_u8_ssim_read(const unsigned long long* cells, double* out, int N, void* stream);
+int bbdm_u8_diversity(const unsigned char* x, unsigned long long* cells, int M, int S, int H, int W, int C, void* stream);
+int bbdm_u8_diversity_read(const unsigned long long* cells, double* out, int M, void* stream);
+
 /* ---- options (no reference counterpart): the library's few integer switches, for tests and tools/ A-B runs ----------------- */
 /* Nothing in the library reads the environment, and no launcher latches a setting: an option is read at every call, so one
  * process can run both sides of an A/B.  Process-wide and unsynchronised.  Names (default):
