@@ -10,7 +10,9 @@ from .sampler import BridgeSampler, SamplingParams  # noqa: F401
 from .latent_cache import CachedPairs, LatentCache  # noqa: F401
 from .optim import EMA, FusedAdam, FusedRMSprop, FusedSGD, get_optimizer  # noqa: F401
 from .metrics import SetEvaluator, diversity, metrics_from_dirs, pair_metrics  # noqa: F401
+from .loss_meter import LossMeter, per_image_loss, validation_loss  # noqa: F401
 
 __all__ = ["BrownianBridgeModel", "LatentBrownianBridgeModel", "UNetModel", "SpatialRescaler", "bridge_schedule",
            "BridgeSampler", "SamplingParams", "philox_normal", "FusedAdam", "FusedSGD", "FusedRMSprop", "EMA", "get_optimizer",
-           "LatentCache", "CachedPairs", "SetEvaluator", "pair_metrics", "diversity", "metrics_from_dirs"]
+           "LatentCache", "CachedPairs", "SetEvaluator", "pair_metrics", "diversity", "metrics_from_dirs",
+           "LossMeter", "per_image_loss", "validation_loss"]

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBDM_HIP_LIB overrides the library path (A/B runs of kernel variants); the default is the in-tree build
 LIB_PATH = os.environ.get("BBDM_HIP_LIB") or os.path.join(_HERE, "libbbdm_hip.so")
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 _P = c_void_p
 # name -> (restype, argtypes); must list every symbol of include/bbdm_hip.h (tests/test_abi.py checks it)
@@ -186,6 +186,10 @@ SIGNATURES = {
     "bbdm_u8_ssim_read": (c_int, [_P, _P, c_int, _P]),
     "bbdm_u8_diversity": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "bbdm_u8_diversity_read": (c_int, [_P, _P, c_int, _P]),
+    # loss by timestep on the device (ABI 33; csrc/loss_meter.hip, bbdm_amd/loss_meter.py)
+    "bbdm_loss_meter_per_image_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "bbdm_loss_meter_accumulate": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "bbdm_loss_meter_read": (c_int, [_P, _P, _P, c_int, _P]),
     "bbdm_opt_chunk_elems": (c_int, []),
     "bbdm_adam_ema_step_f32": (c_int, [_P, c_int, c_int, c_double, c_double, c_double, c_double, c_double,
                                        ctypes.c_longlong, c_int, c_double, _P]),

@@ -211,9 +211,27 @@ class BrownianBridgeModel(nn.Module):
             recloss = bb_loss(objective, objective_recon, self.loss_type)
         else:
             recloss = self._loss(objective, objective_recon)
+        meter = self._loss_meters[0 if self.training else 1]
+        if meter is not None:                  # the loss by timestep (bbdm_amd/loss_meter.py): two launches, no read-back
+            meter.add(objective, objective_recon.detach(), t, loss_type=self.loss_type)
         x0_recon = self.predict_x0_from_objective(x_t, y, t, objective_recon.detach())
         log_dict = {"loss": recloss, "x0_recon": x0_recon}
         return recloss, log_dict
+
+    # ---- loss meters (bbdm_amd/loss_meter.py) -----------------------------------------------------------
+    _loss_meters = (None, None)
+
+    def attach_loss_meter(self, train=None, val=None):
+        """From here on every loss evaluation (``forward``, ``p_losses``, ``p_losses_cached``) also adds its per-image losses and their
+        ``t`` to a :class:`bbdm_amd.LossMeter`: ``train`` while ``self.training``, ``val`` otherwise; either may be None.  The loss,
+        its gradient and the keys of ``log_dict`` are what they are without a meter."""
+        for m in (train, val):
+            if m is not None and m.num_timesteps != self.num_timesteps:
+                raise ValueError(f"the meter buckets {m.num_timesteps} timesteps, the model has {self.num_timesteps}")
+        self._loss_meters = (train, val)
+
+    def detach_loss_meter(self):
+        self._loss_meters = (None, None)
 
     def _loss(self, a, b):
         _need_gpu(a, b)
@@ -223,6 +241,13 @@ class BrownianBridgeModel(nn.Module):
         _launch(a, "bbdm_bb_loss_f32", a.data_ptr(), b.data_ptr(), partial_.data_ptr(), out.data_ptr(), a.numel(),
                   _LOSSES[self.loss_type])
         return out[0]
+
+    def _table_index(self, t):
+        """``t`` as the contiguous int64 index the kernels read ``m_t`` / ``variance_t`` with, clamped to ``[0, num_timesteps)`` on the
+        device (one small launch, no sync).  The kernels take the tables as bare pointers: an out-of-range ``t`` -- where the reference
+        raises from its gather -- read whatever lay beside the tables, so a result could depend on the heap's layout.  In-range ``t``
+        is unchanged; the UNet's timestep embedding and an attached loss meter (which rejects it) still see the caller's ``t``."""
+        return t.to(torch.int64).clamp(0, self.num_timesteps - 1).contiguous()
 
     def q_sample(self, x0, y, t, noise=None, seeds=None, ordinals=None):
         """BrownianBridgeModel.py:128-146 -> (x_t, objective).  With ``seeds``: noise = philox_normal(shape, seeds, ordinals,
@@ -238,7 +263,7 @@ class BrownianBridgeModel(nn.Module):
         noise = torch.randn_like(x0) if noise is None else noise
         _need_gpu(x0, y, noise, t)
         x0c, yc, nc = _f32c(x0), _f32c(y), _f32c(noise)
-        tc = t.to(torch.int64).contiguous()
+        tc = self._table_index(t)
         x_t, target = torch.empty_like(x0c), torch.empty_like(x0c)
         _launch(x0c, "bbdm_bb_q_sample_f32", x0c.data_ptr(), yc.data_ptr(), nc.data_ptr(), tc.data_ptr(),
                   self.m_t.data_ptr(), self.variance_t.data_ptr(), x_t.data_ptr(), target.data_ptr(),
@@ -248,7 +273,7 @@ class BrownianBridgeModel(nn.Module):
     def _q_sample_seeded(self, x0, y, t, seeds, ordinals):
         _need_gpu(x0, y, t)
         x0c, yc = _f32c(x0), _f32c(y)
-        tc = t.to(torch.int64).contiguous()
+        tc = self._table_index(t)
         n = x0c.shape[0]
         sd = _i64_per_image(seeds, n, x0c.device, "seeds")
         od = _i64_per_image(ordinals, n, x0c.device, "ordinals")
@@ -264,7 +289,7 @@ class BrownianBridgeModel(nn.Module):
             raise NotImplementedError
         _need_gpu(x_t, y, objective_recon, t)
         a, b, p = _f32c(x_t), _f32c(y), _f32c(objective_recon)
-        tc = t.to(torch.int64).contiguous()
+        tc = self._table_index(t)
         out = torch.empty_like(a)
         _launch(a, "bbdm_bb_predict_x0_f32", a.data_ptr(), b.data_ptr(), p.data_ptr(), tc.data_ptr(),
                   self.m_t.data_ptr(), self.variance_t.data_ptr(), out.data_ptr(), a.shape[0], a[0].numel(),
@@ -492,7 +517,8 @@ class LatentBrownianBridgeModel(BrownianBridgeModel):
         _need_gpu(ori, cond, tc)
         x_t, target, y = (torch.empty((n,) + tuple(ori.shape[1:]), dtype=torch.float32, device=dev) for _ in range(3))
         head = (ori.data_ptr(), cond.data_ptr(), M, io.data_ptr(), ic.data_ptr(), *(None if v is None else v.data_ptr() for v in stats), hw)
-        tail = (tc.data_ptr(), self.m_t.data_ptr(), self.variance_t.data_ptr(), x_t.data_ptr(), target.data_ptr(), y.data_ptr(),
+        tq = self._table_index(tc)
+        tail = (tq.data_ptr(), self.m_t.data_ptr(), self.variance_t.data_ptr(), x_t.data_ptr(), target.data_ptr(), y.data_ptr(),
                 n, C * hw, _OBJECTIVES[self.objective])
         if seeds is not None:
             sd = _i64_per_image(seeds, n, dev, "seeds")

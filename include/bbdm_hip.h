@@ -806,6 +806,30 @@ int bbdm_u8_ssim_read(const unsigned long long* cells, double* out, int N, void*
 int bbdm_u8_diversity(const unsigned char* x, unsigned long long* cells, int M, int S, int H, int W, int C, void* stream);
 int bbdm_u8_diversity_read(const unsigned long long* cells, double* out, int M, void* stream);
 
+/* ---- loss by timestep, accumulated on the device (ABI 33; csrc/loss_meter.hip, bbdm_amd/loss_meter.py) -------- */
+/* The reference logs the batch mean of the loss at whatever t each image drew and reads it back every micro-step
+ * (BrownianBridgeModel.py:114-117, BaseRunner.py:417-436).  These three keep a table over buckets of t on the device, next to the
+ * scalar loss (bbdm_bb_loss_f32 is unchanged and still produces it).  Every accumulator is DEVICE memory the CALLER owns; sums are
+ * csrc/stats_acc.h cells of 4 64-bit words, so a result depends on the values added and not on their order or grouping.
+ *   bbdm_loss_meter_per_image_f32 : a, b fp32 [N][per_sample] contiguous; loss_type 0 = |a - b|, 1 = (a - b)^2 (difference in fp32,
+ *                                   sum in fp64, as bbdm_bb_loss_f32).  cells[N][4], ZEROED by the caller, += the fp64 partial of
+ *                                   each 2048-element chunk of image n: the chunks, their elements and the order of the additions
+ *                                   inside one depend on per_sample alone, so cells[n] is a function of the values of image n
+ *                                   whatever N, n or the alignment (16-byte loads when per_sample % 4 == 0 and a, b are 16-byte
+ *                                   aligned, element loads otherwise: same bits).  per_image (NULL = skip): [N] fp32 =
+ *                                   (float)(fold(cells[n]) / per_sample), NaN for an image with a non-finite term;
+ *   bbdm_loss_meter_accumulate    : t int64 [N]; for every image v = fold(cells[n]) / per_sample in fp64, bucket = (t * B) / T in
+ *                                   64-bit integers; meter[bucket][0] += v, meter[bucket][1] += v * v (limb cells), counts[bucket]
+ *                                   += 1.  t outside [0, T), compared as int64: no bucket is touched, counts[B] += 1.  A non-finite
+ *                                   v marks the bucket's cells, which then read NaN until the caller zeroes them.  meter [B][2][4]
+ *                                   and counts [B + 1] 64-bit words persist across calls; at most 2^23 additions per bucket;
+ *   bbdm_loss_meter_read          : sum[B], sumsq[B] (fp64, device) = the folded cells. */
+int bbdm_loss_meter_per_image_f32(const float* a, const float* b, unsigned long long* cells, float* per_image, int N,
+                                  int per_sample, int loss_type, void* stream);
+int bbdm_loss_meter_accumulate(const unsigned long long* cells, const int64_t* t, unsigned long long* meter,
+                               unsigned long long* counts, int N, int per_sample, int T, int B, void* stream);
+int bbdm_loss_meter_read(const unsigned long long* meter, double* sum, double* sumsq, int B, void* stream);
+
 /* ---- options (no reference counterpart): the library's few integer switches, for tests and tools/ A-B runs ----------------- */
 /* Nothing in the library reads the environment, and no launcher latches a setting: an option is read at every call, so one
  * process can run both sides of an A/B.  Process-wide and unsynchronised.  Names (default):
