@@ -15,6 +15,7 @@
 // for step r makes register r of P^T exactly the B operand of step r -- no LDS round trip, no shuffles; row
 // max / sum are 15 VALU ops + one cross-half exchange.  The running max / sum / rescale are per-lane scalars.
 #include "bf3_split.h"
+#include "dispatch.h"
 #include "h2_split.h"
 #include "lds_dma.h"
 #include <stdlib.h>
@@ -690,25 +691,21 @@ static int launch_attention(const float* q, int ldq, int hsq, const float* k, co
     const bool pipe = bbdm_option(BBDM_OPT_ATTN_PIPE) != 0;           // the interleaved main loop (PIPE) of the full bf16x3 path (2: + the pre-split entry points)
     // 4 waves (128 queries) per workgroup, three workgroups per CU (an 8-wave / 256-query form, K / V staged once per 256 queries,
     // measured 6.55 against 6.16 ms at C2 in round 3 and is gone)
-    const int nw = 4;
+    constexpr int nw = 4;
     const int qblocks = (Tq + nw * 32 - 1) / (nw * 32);
     const int nht = N * heads;
     const dim3 grid((unsigned)(8ll * ((nht + 7) / 8) * qblocks));
-#define BBDM_ATTN_FWD(CH, BQ, BV, NW)                                                                                      \
-    hipLaunchKernelGGL((attn_fwd_kernel<CH, BQ, BV, NW>), grid, dim3(NW * 64), 0, st, q, ldq, hsq, k, v, ldkv, hskv, out, ldo, \
-                       lse, Tq, Tk, heads, nht, qscale, kscale)
-#define BBDM_ATTN_FWD_NW(CH, BQ, BV) BBDM_ATTN_FWD(CH, BQ, BV, 4)
-#define BBDM_ATTN_FWD_P(CH)                                                                                                  \
-    hipLaunchKernelGGL((attn_fwd_kernel<CH, true, true, 4, true>), grid, dim3(4 * 64), 0, st, q, ldq, hsq, k, v, ldkv, hskv, out, ldo, \
-                       lse, Tq, Tk, heads, nht, qscale, kscale)
-    if (ch == 128) { if (bq == 1 && pipe) BBDM_ATTN_FWD_P(128); else if (bq == 1) BBDM_ATTN_FWD_NW(128, true, true); else if (bq) BBDM_ATTN_FWD_NW(128, true, false); else BBDM_ATTN_FWD_NW(128, false, false); }
-    else if (ch == 64) { if (bq == 1 && pipe) BBDM_ATTN_FWD_P(64); else if (bq == 1) BBDM_ATTN_FWD_NW(64, true, true); else if (bq) BBDM_ATTN_FWD_NW(64, true, false); else BBDM_ATTN_FWD_NW(64, false, false); }
-    else if (ch == 32) { if (bq == 1 && pipe) BBDM_ATTN_FWD_P(32); else if (bq == 1) BBDM_ATTN_FWD_NW(32, true, true); else if (bq) BBDM_ATTN_FWD_NW(32, true, false); else BBDM_ATTN_FWD_NW(32, false, false); }
-#undef BBDM_ATTN_FWD_P
-    else { if (bq) BBDM_ATTN_FWD_NW(16, true, false); else BBDM_ATTN_FWD_NW(16, false, false); }
-#undef BBDM_ATTN_FWD_NW
-#undef BBDM_ATTN_FWD
-    return 0;
+    // operand form: 0 = both products on the f32 MFMA, 1 = Q K^T on bf16x3, 2 = P V as well, 3 = 2 with the interleaved main loop
+    // (16-channel heads have forms 0 and 1 only)
+    const int form = !bq ? 0 : (bq != 1 || ch == 16) ? 1 : pipe ? 3 : 2;
+    auto launch = [&](auto CH, auto FORM) {
+        constexpr int F = FORM();
+        hipLaunchKernelGGL((attn_fwd_kernel<CH(), (F >= 1), (F >= 2), nw, (F == 3)>), grid, dim3(nw * 64), 0, st, q, ldq, hsq, k, v, ldkv,
+                           hskv, out, ldo, lse, Tq, Tk, heads, nht, qscale, kscale);
+        return BBDM_OK;
+    };
+    if (ch == 16) return dispatch([&](auto FORM) { return launch(int_c<16>, FORM); }, one_of<0, 1>(form));
+    return dispatch(launch, one_of<128, 64, 32>(ch), one_of<0, 1, 2, 3>(form));
 }
 
 extern "C" int bbdm_attention_f32(const float* qkv, int ldq, float* out, int ldo, float* lse, int N, int T, int heads,
@@ -764,13 +761,12 @@ static int attn_kv_planes(const float* qkv, int ldq, void* planes, size_t planes
     const float* v = new_order ? qkv + 2 * C : qkv + 2 * ch;
     const int hs = new_order ? ch : 3 * ch;
     const dim3 grid((unsigned)(N * heads * (T / 32)));
-#define BBDM_ATTN_KV(CH, NP) hipLaunchKernelGGL((attn_kv_planes_kernel<CH, NP>), grid, dim3(256), 0, (hipStream_t)stream, k, v, ldq, hs, (unsigned char*)planes, T, heads, scale, bound)
-    if (ch == 128) { if (bound) BBDM_ATTN_KV(128, 2); else BBDM_ATTN_KV(128, 3); }
-    else if (ch == 64) { if (bound) BBDM_ATTN_KV(64, 2); else BBDM_ATTN_KV(64, 3); }
-    else { if (bound) BBDM_ATTN_KV(32, 2); else BBDM_ATTN_KV(32, 3); }
-#undef BBDM_ATTN_KV
-    BBDM_CHECK_LAUNCH("attention_kv_planes");
-    return BBDM_OK;
+    return dispatch([&](auto CH, auto NP) {
+        hipLaunchKernelGGL((attn_kv_planes_kernel<CH(), NP()>), grid, dim3(256), 0, (hipStream_t)stream, k, v, ldq, hs, (unsigned char*)planes,
+                           T, heads, scale, bound);
+        BBDM_CHECK_LAUNCH("attention_kv_planes");
+        return BBDM_OK;
+    }, one_of<128, 64, 32>(ch), one_of<2, 3>(bound ? 2 : 3));
 }
 static int attn_planes(const float* qkv, int ldq, float* out, int ldo, float* lse, int N, int T, int heads, int ch, int new_order,
                        const void* planes, const float* bound, void* stream) {
@@ -782,25 +778,15 @@ static int attn_planes(const float* qkv, int ldq, float* out, int ldo, float* ls
     const int nht = N * heads, qblocks = T / 128;
     const dim3 grid((unsigned)(8ll * ((nht + 7) / 8) * qblocks));
     const int hsq = new_order ? ch : 3 * ch;
-#define BBDM_ATTN_PL(CH, NP) hipLaunchKernelGGL((attn_fwd_planes_kernel<CH, NP>), grid, dim3(256), attn_planes_lds(CH, NP), (hipStream_t)stream, qkv, ldq, hsq, (const unsigned char*)planes, out, ldo, lse, T, heads, nht, scale, bound)
-    if (ch == 128) {         // 96 / 64 KB of dynamic LDS: above the default limit, raised once per device
-        static bool lds_set_dev[BBDM_MAX_DEVICES] = {};
-        bool& lds_set = lds_set_dev[bbdm_device_slot()];
-        if (!lds_set) {
-            BBDM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_planes_kernel<128, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)attn_planes_lds(128, 3)) == hipSuccess &&
-                             hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_planes_kernel<128, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)attn_planes_lds(128, 2)) == hipSuccess,
-                         "attention_planes: hipFuncSetAttribute(%zu B LDS) failed", attn_planes_lds(128, 3));
-            lds_set = true;
-        }
-        if (bound) BBDM_ATTN_PL(128, 2); else BBDM_ATTN_PL(128, 3);
-    }
-    else if (ch == 64) { if (bound) BBDM_ATTN_PL(64, 2); else BBDM_ATTN_PL(64, 3); }
-    else { if (bound) BBDM_ATTN_PL(32, 2); else BBDM_ATTN_PL(32, 3); }
-#undef BBDM_ATTN_PL
-    BBDM_CHECK_LAUNCH("attention_planes");
-    return BBDM_OK;
+    return dispatch([&](auto CH, auto NP) {
+        const size_t lds = attn_planes_lds(CH(), NP());
+        if constexpr (CH() == 128)      // 96 / 64 KB of dynamic LDS: above the default limit
+            if (const int rc = bbdm_ensure_lds<attn_fwd_planes_kernel<128, NP()>>(lds, "attention_planes")) return rc;
+        hipLaunchKernelGGL((attn_fwd_planes_kernel<CH(), NP()>), grid, dim3(256), lds, (hipStream_t)stream, qkv, ldq, hsq,
+                           (const unsigned char*)planes, out, ldo, lse, T, heads, nht, scale, bound);
+        BBDM_CHECK_LAUNCH("attention_planes");
+        return BBDM_OK;
+    }, one_of<128, 64, 32>(ch), one_of<2, 3>(bound ? 2 : 3));
 }
 extern "C" int bbdm_attention_kv_planes_f32(const float* qkv, int ldq, void* planes, size_t planes_bytes, int N, int T, int heads, int ch,
                                             int new_order, void* stream) {

@@ -15,6 +15,7 @@
 //   attn_bwd_dq  : workgroup = 128 queries, streams key tiles   -> dq
 //   attn_bwd_dkv : workgroup = 128 keys,    streams query tiles -> dk, dv
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -344,11 +345,10 @@ int attention_bwd_common(const float* q, int ldq, int hsq, const float* k, const
     int pb = (int)((total + 255) / 256);
     if (pb > 4096) pb = 4096;
     hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(pb), dim3(256), 0, st, out, ldo, dout, lddo, dwork, N, Tq, heads, ch);
-#define BBDM_ATTN_BWD(CH) \
-    launch_bwd<CH>(q, ldq, hsq, k, v, ldkv, hskv, dout, lddo, lse, dwork, dq, lddq, dk, dv, lddkv, N, Tq, Tk, heads, qscale, kscale, st)
-    if (ch == 128) BBDM_ATTN_BWD(128); else if (ch == 64) BBDM_ATTN_BWD(64); else if (ch == 32) BBDM_ATTN_BWD(32); else BBDM_ATTN_BWD(16);
-#undef BBDM_ATTN_BWD
-    return 0;
+    return dispatch([&](auto CH) {
+        launch_bwd<CH()>(q, ldq, hsq, k, v, ldkv, hskv, dout, lddo, lse, dwork, dq, lddq, dk, dv, lddkv, N, Tq, Tk, heads, qscale, kscale, st);
+        return BBDM_OK;
+    }, one_of<128, 64, 32, 16>(ch));
 }
 
 }  // namespace

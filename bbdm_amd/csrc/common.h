@@ -41,6 +41,20 @@ static inline int bbdm_device_slot() {
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= BBDM_MAX_DEVICES) d = 0;
     return d;
 }
+// Raise the dynamic-LDS limit of one kernel INSTANCE (a non-type parameter: instances with equal signatures share a type) to `bytes`
+// on the current device, unless it already stands at that or more; launchers call it for the instance they are about to launch.
+template <auto Kernel>
+static inline int bbdm_ensure_lds(size_t bytes, const char* what) {
+    static size_t set_dev[BBDM_MAX_DEVICES] = {};
+    size_t& set = set_dev[bbdm_device_slot()];
+    if (bytes <= set) return BBDM_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        bbdm_set_error("%s: hipFuncSetAttribute(%zu B LDS) failed", what, bytes);
+        return BBDM_E_LAUNCH;
+    }
+    set = bytes;
+    return BBDM_OK;
+}
 
 // winograd_wgrad.hip: bbdm_gemm_tn_batched_f32 + the column sums of B per K split (internal; conv_wgrad.hip's 1x1 path)
 int bbdm_gemm_tn_impl(const float* A, int lda, size_t a_stride, const float* B, int ldb, size_t b_stride, float* C, float* bias_part,

@@ -22,6 +22,7 @@
 //     blocks share a CU (<=75 KB LDS, <=128 VGPR each): 4 waves per SIMD cover each other's barriers.
 #include <stdlib.h>
 #include "common.h"
+#include "dispatch.h"
 #include "stats_acc.h"
 
 namespace {
@@ -802,17 +803,15 @@ __global__ void __launch_bounds__(256) conv3x3_narrow_small_kernel(const ConvArg
     }
 }
 
-template <int CO>
+template <int CO, bool PRE>
 void launch_narrow(const ConvArgs& a, hipStream_t st) {
     if ((long long)a.N * a.H * a.W < 65536) {                    // small images: 8 x 8 tiles, the chunks split over the four waves
         const dim3 grid8((unsigned)(cdiv(a.W, 8) * cdiv(a.H, 8)), (unsigned)a.N);
-        if (a.pre_sc) hipLaunchKernelGGL((conv3x3_narrow_small_kernel<CO, true>), grid8, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv3x3_narrow_small_kernel<CO, false>), grid8, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((conv3x3_narrow_small_kernel<CO, PRE>), grid8, dim3(256), 0, st, a);
         return;
     }
     const dim3 grid((unsigned)(cdiv(a.W, 16) * cdiv(a.H, 16)), (unsigned)a.N);
-    if (a.pre_sc) hipLaunchKernelGGL((conv3x3_narrow_kernel<CO, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_narrow_kernel<CO, false>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((conv3x3_narrow_kernel<CO, PRE>), grid, dim3(256), 0, st, a);
 }
 
 // out = sum_s ws[s] + bias (+ residual): fixed summation order -> deterministic
@@ -836,27 +835,11 @@ __global__ void conv_splitk_reduce_kernel(const ConvArgs a) {
     }
 }
 
-template <typename K>
-int set_lds_limit(K kernel, size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)bytes) == hipSuccess
-               ? 0
-               : -1;
-}
-
 template <int BM, int BN, int WM, int WN, int PSLOTS, int OCC, int VAR>
 int launch_variant(const ConvArgs& a, size_t lds, long long blocks, hipStream_t stream) {
-    auto kern = conv_igemm_f32<BM, BN, WM, WN, PSLOTS, OCC, VAR>;
-    static size_t lds_set_dev[BBDM_MAX_DEVICES] = {};
-    size_t& lds_set = lds_set_dev[bbdm_device_slot()];
-    if (lds > lds_set) {
-        if (set_lds_limit(kern, lds) != 0) {
-            bbdm_set_error("conv: hipFuncSetAttribute(%zu B LDS) failed", lds);
-            return BBDM_E_LAUNCH;
-        }
-        lds_set = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, a.splits, a.batch), dim3(WM * WN * 64), lds, stream, a);
+    if (const int rc = bbdm_ensure_lds<conv_igemm_f32<BM, BN, WM, WN, PSLOTS, OCC, VAR>>(lds, "conv")) return rc;
+    hipLaunchKernelGGL((conv_igemm_f32<BM, BN, WM, WN, PSLOTS, OCC, VAR>), dim3((unsigned)blocks, a.splits, a.batch), dim3(WM * WN * 64), lds,
+                       stream, a);
     return 0;
 }
 
@@ -1085,23 +1068,21 @@ extern "C" int bbdm_conv2d_nhwc_stats_f32(const float* x, int ldx, const float* 
     const long long M = (long long)N * H * W;
     const long long narrow_min = 4096;       // (below: the general implicit GEMM; measured slower from 8192 pixels)
     if (ks == 3 && Cout <= 8 && !residual && M >= narrow_min) {      // a few output channels: one thread per pixel (see above)
-        if (Cout <= 3) launch_narrow<3>(a, st); else if (Cout <= 4) launch_narrow<4>(a, st); else launch_narrow<8>(a, st);
-        BBDM_CHECK_LAUNCH("conv2d(narrow)");
-        return BBDM_OK;
+        return dispatch([&](auto CO, auto PRE) {
+            launch_narrow<CO(), PRE()>(a, st);
+            BBDM_CHECK_LAUNCH("conv2d(narrow)");
+            return BBDM_OK;
+        }, one_of<3, 4, 8>(Cout <= 3 ? 3 : Cout <= 4 ? 4 : 8), a.pre_sc != nullptr);
     }
     if (ks == 3 && (CinPad == 8 || CinPad == 4) && Cout == 128 && !residual && !pre_scale && out_nchw == 0 && M >= 4096) {
         const int tiles = N * cdiv(H, 16) * cdiv(W, 16);         // the stem: K = 72 / 36 in one stage (conv3x3_stem_kernel)
         const dim3 grid((unsigned)(tiles < 512 ? tiles : 512));
         const bool stats = stats0 || stats1;
-        if (CinPad == 8) {
-            if (stats) hipLaunchKernelGGL((conv3x3_stem_kernel<8, true>), grid, dim3(256), 0, st, a, tiles);
-            else hipLaunchKernelGGL((conv3x3_stem_kernel<8, false>), grid, dim3(256), 0, st, a, tiles);
-        } else {
-            if (stats) hipLaunchKernelGGL((conv3x3_stem_kernel<4, true>), grid, dim3(256), 0, st, a, tiles);
-            else hipLaunchKernelGGL((conv3x3_stem_kernel<4, false>), grid, dim3(256), 0, st, a, tiles);
-        }
-        BBDM_CHECK_LAUNCH("conv2d(stem)");
-        return BBDM_OK;
+        return dispatch([&](auto CIN, auto STATS) {
+            hipLaunchKernelGGL((conv3x3_stem_kernel<CIN(), STATS()>), grid, dim3(256), 0, st, a, tiles);
+            BBDM_CHECK_LAUNCH("conv2d(stem)");
+            return BBDM_OK;
+        }, one_of<8, 4>(CinPad), stats);
     }
     const ConvPlan plan = conv_plan(M, Cout, a.nchunks);
     a.splits = plan.splits;

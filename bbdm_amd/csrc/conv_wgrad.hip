@@ -16,6 +16,7 @@
 // gridDim.z; partial tiles go to a workspace and a second kernel sums the splits in a fixed order (deterministic)
 // while transposing to the parameter's OIHW layout.
 #include "common.h"
+#include "dispatch.h"
 #include "stats_acc.h"
 #include "bf3_split.h"
 #include <stdlib.h>
@@ -660,16 +661,7 @@ static int launch_wgrad(const WgradArgs& a, dim3 grid, hipStream_t st) {
     constexpr int PAD = TAPS == 9 ? 1 : 0;
     constexpr int XPIX = (PTW + 2 * PAD) * (PTH + 2 * PAD);
     constexpr size_t lds = ((size_t)2 * XPIX * (WI * 32 + 4) + 2 * PTH * PTW * CP) * sizeof(float);
-    static bool attr_set_dev[BBDM_MAX_DEVICES] = {};
-    bool& attr_set = attr_set_dev[bbdm_device_slot()];
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_f32<TAPS, WI>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            bbdm_set_error("conv_wgrad: hipFuncSetAttribute(%zu B LDS) failed", lds);
-            return BBDM_E_LAUNCH;
-        }
-        attr_set = true;
-    }
+    if (const int rc = bbdm_ensure_lds<conv_wgrad_f32<TAPS, WI>>(lds, "conv_wgrad")) return rc;
     hipLaunchKernelGGL((conv_wgrad_f32<TAPS, WI>), grid, dim3(WI * 128), lds, st, a);
     return 0;
 }
@@ -750,8 +742,8 @@ extern "C" int bbdm_conv_wgrad_f32(const float* x, int ldx, const float* dy, int
         hipLaunchKernelGGL((conv_wgrad_thin_f32<1>), dim3(cdiv(Cin, 128), 1, splits), dim3(256), 0, st, a);
     } else {
         const dim3 grid(a.CinP / g.cti, a.CoutP / CT, splits);
-        if (ks == 3) rc = g.cti == 128 ? launch_wgrad<9, 4>(a, grid, st) : launch_wgrad<9, 2>(a, grid, st);
-        else rc = g.cti == 128 ? launch_wgrad<1, 4>(a, grid, st) : launch_wgrad<1, 2>(a, grid, st);
+        rc = dispatch([&](auto TAPS, auto WI) { return launch_wgrad<TAPS(), WI()>(a, grid, st); }, one_of<9, 1>(ks * ks),
+                      one_of<4, 2>(g.cti == 128 ? 4 : 2));
     }
     if (rc != 0) return rc;
     const size_t total = (size_t)Cout * Cin * ks * ks;

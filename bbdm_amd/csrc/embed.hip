@@ -4,6 +4,7 @@
 // and every ResBlock's emb_layers = SiLU -> Linear (openaimodel.py:221-227,267).  The 21 per-block projections
 // share one input, so the host concatenates their weights once and issues ONE call ([N,512] x [512, sum 2*Cout]).
 #include "common.h"
+#include "dispatch.h"
 #include <stdlib.h>
 
 namespace {
@@ -409,31 +410,15 @@ extern "C" int bbdm_linear_bwd_f32(const float* dy, const float* x, const float*
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)((N + 1) & ~1) * In * sizeof(float);
     BBDM_REQUIRE(lds <= 160 * 1024, "linear_bwd: N*In too large for LDS staging");
-    static size_t lds_set_dev[BBDM_MAX_DEVICES] = {};
-    size_t& lds_set = lds_set_dev[bbdm_device_slot()];
-    if (lds > 64 * 1024 && lds > lds_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bwd_w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) {
-            bbdm_set_error("linear_bwd: hipFuncSetAttribute failed");
-            return BBDM_E_LAUNCH;
-        }
-        lds_set = lds;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = bbdm_ensure_lds<linear_bwd_w_kernel>(lds, "linear_bwd")) return rc;
     const int otiles = cdiv(Out, 32);
     hipLaunchKernelGGL(linear_bwd_w_kernel, dim3(otiles < 512 ? otiles : 512), dim3(256), lds, st, dy, x, dw, db, N, In, Out, act_in);
     if (dx) {
         const int chunks = cdiv(Out, LB_OCH);
         const size_t lds_x = (size_t)(N > 32 ? 64 : 32) * LB_PITCH * sizeof(float);
-        static bool x_attr_dev[BBDM_MAX_DEVICES] = {};
-        bool& x_attr = x_attr_dev[bbdm_device_slot()];
-        if (lds_x > 64 * 1024 && !x_attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bwd_x_partial_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x) != hipSuccess) {
-                bbdm_set_error("linear_bwd: hipFuncSetAttribute failed");
-                return BBDM_E_LAUNCH;
-            }
-            x_attr = true;
-        }
+        if (lds_x > 64 * 1024)
+            if (const int rc = bbdm_ensure_lds<linear_bwd_x_partial_kernel>(lds_x, "linear_bwd")) return rc;
         hipLaunchKernelGGL(linear_bwd_x_partial_kernel, dim3(cdiv(In, 128), chunks), dim3(256), lds_x, st, dy, w, ws, N, In, Out);
         hipLaunchKernelGGL(linear_bwd_x_final_kernel, dim3(cdiv(N * In, 256)), dim3(256), 0, st, ws, x, dx, chunks, N, In,
                            act_in);
@@ -463,22 +448,15 @@ extern "C" int bbdm_linear_f32(const float* x, const float* w, const float* b, f
         // walk the whole K -- and the thread-per-(row, output) kernel below wins: 21.8 -> 12.9 us at batch 32, 16.1 -> 6.7 at batch 4)
         const int mfma_min_out = 2048;
         if (In % 8 == 0 && In >= 64 && Out >= mfma_min_out && (((uintptr_t)w & 15) == 0) && lds_m <= 160 * 1024) {
-            static size_t lds_m_dev[BBDM_MAX_DEVICES][2] = {};
-            size_t& have = lds_m_dev[bbdm_device_slot()][MB - 1];
-            if (lds_m > 64 * 1024 && lds_m > have) {
-                const void* f = MB == 2 ? reinterpret_cast<const void*>(linear_mfma_kernel<2>) : reinterpret_cast<const void*>(linear_mfma_kernel<1>);
-                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m) != hipSuccess) {
-                    bbdm_set_error("linear: hipFuncSetAttribute(%zu) failed", lds_m);
-                    return BBDM_E_LAUNCH;
-                }
-                have = lds_m;
-            }
-            const int otiles = cdiv(Out, 32);
-            const dim3 grid(cdiv(otiles, 4) < 256 ? cdiv(otiles, 4) : 256);
-            if (MB == 2) hipLaunchKernelGGL(linear_mfma_kernel<2>, grid, dim3(256), lds_m, st, x, w, b, y, N, In, Out, act_in, act_out);
-            else hipLaunchKernelGGL(linear_mfma_kernel<1>, grid, dim3(256), lds_m, st, x, w, b, y, N, In, Out, act_in, act_out);
-            BBDM_CHECK_LAUNCH("linear(mfma)");
-            return BBDM_OK;
+            return dispatch([&](auto MB_) {
+                if (lds_m > 64 * 1024)
+                    if (const int rc = bbdm_ensure_lds<linear_mfma_kernel<MB_()>>(lds_m, "linear")) return rc;
+                const int otiles = cdiv(Out, 32);
+                const dim3 grid(cdiv(otiles, 4) < 256 ? cdiv(otiles, 4) : 256);
+                hipLaunchKernelGGL(linear_mfma_kernel<MB_()>, grid, dim3(256), lds_m, st, x, w, b, y, N, In, Out, act_in, act_out);
+                BBDM_CHECK_LAUNCH("linear(mfma)");
+                return BBDM_OK;
+            }, one_of<2, 1>(MB));
         }
     }
     const size_t lds = (size_t)N * (In + 4) * sizeof(float);
@@ -486,23 +464,14 @@ extern "C" int bbdm_linear_f32(const float* x, const float* w, const float* b, f
     const int NBl = ilog2(ceil_pow2(N));
     const int outs_per_block = 256 >> NBl;
     const bool vec = (In % 4 == 0) && (((uintptr_t)w & 15) == 0);
-    static size_t lds_set_dev[BBDM_MAX_DEVICES][2] = {};
-    size_t (&lds_set)[2] = lds_set_dev[bbdm_device_slot()];
-    if (lds > 64 * 1024 && lds > lds_set[vec]) {
-        const void* f = vec ? reinterpret_cast<const void*>(linear_kernel<1>) : reinterpret_cast<const void*>(linear_kernel<0>);
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            bbdm_set_error("linear: hipFuncSetAttribute(%zu) failed", lds);
-            return BBDM_E_LAUNCH;
-        }
-        lds_set[vec] = lds;
-    }
-    const dim3 grid(cdiv(Out, outs_per_block));
-    if (vec)
-        hipLaunchKernelGGL(linear_kernel<1>, grid, dim3(256), lds, st, x, w, b, y, N, In, Out, NBl, act_in, act_out);
-    else
-        hipLaunchKernelGGL(linear_kernel<0>, grid, dim3(256), lds, st, x, w, b, y, N, In, Out, NBl, act_in, act_out);
-    BBDM_CHECK_LAUNCH("linear");
-    return BBDM_OK;
+    return dispatch([&](auto VEC) {
+        if (lds > 64 * 1024)
+            if (const int rc = bbdm_ensure_lds<linear_kernel<VEC()>>(lds, "linear")) return rc;
+        const dim3 grid(cdiv(Out, outs_per_block));
+        hipLaunchKernelGGL(linear_kernel<VEC()>, grid, dim3(256), lds, st, x, w, b, y, N, In, Out, NBl, act_in, act_out);
+        BBDM_CHECK_LAUNCH("linear");
+        return BBDM_OK;
+    }, one_of<1, 0>(vec));
 }
 
 // bbdm_linear_f32 on weights packed once (inference: static weights).  packed = bbdm_linear_pack_f32(w) holds
@@ -528,16 +497,8 @@ extern "C" int bbdm_linear_packed_f32(const float* x, const void* packed, const 
     BBDM_REQUIRE(bbdm_linear_packed_supported(N, In, Out) && ((uintptr_t)packed & 15) == 0, "linear_packed: N=%d In=%d Out=%d unsupported",
                  N, In, Out);
     const size_t lds = (((size_t)32 * (In + 1) * 4 + 15) & ~(size_t)15) + (size_t)4 * LP_NS * LP_BLOCK;
-    static size_t lds_dev[BBDM_MAX_DEVICES] = {};
-    size_t& have = lds_dev[bbdm_device_slot()];
-    if (lds > 64 * 1024 && lds > have) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-            bbdm_set_error("linear_packed: hipFuncSetAttribute(%zu) failed", lds);
-            return BBDM_E_LAUNCH;
-        }
-        have = lds;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = bbdm_ensure_lds<linear_packed_kernel>(lds, "linear_packed")) return rc;
     const int otiles = (Out + 31) / 32;
     hipLaunchKernelGGL(linear_packed_kernel, dim3((unsigned)((otiles + 3) / 4)), dim3(256), lds, (hipStream_t)stream, x,
                        (const unsigned char*)packed, b, y, N, In, Out, act_in, act_out);

@@ -10,6 +10,7 @@
 //     d = sum(z^2, 1) + sum(e^2, 1) - 2 z e^T;  argmin_j d
 // e_dim is 3..8: one thread evaluates a pixel against the codebook streamed through LDS.
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -108,15 +109,9 @@ extern "C" int bbdm_vq_nearest_f32(const float* z, int ldz, const float* codeboo
     long long blocks = (pixels + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipStream_t st = (hipStream_t)stream;
-#define BBDM_VQ(D)                                                                                                          \
-    case D:                                                                                                                 \
-        hipLaunchKernelGGL(vq_argmin_kernel<D>, dim3((unsigned)blocks), dim3(256), 0, st, z, ldz, codebook, indices, zq, ldq, \
-                           pixels, n_e);                                                                                    \
-        break;
-    switch (e_dim) {
-        BBDM_VQ(1) BBDM_VQ(2) BBDM_VQ(3) BBDM_VQ(4) BBDM_VQ(5) BBDM_VQ(6) BBDM_VQ(7) BBDM_VQ(8)
-    }
-#undef BBDM_VQ
-    BBDM_CHECK_LAUNCH("vq_nearest");
-    return BBDM_OK;
+    return dispatch([&](auto D) {
+        hipLaunchKernelGGL(vq_argmin_kernel<D()>, dim3((unsigned)blocks), dim3(256), 0, st, z, ldz, codebook, indices, zq, ldq, pixels, n_e);
+        BBDM_CHECK_LAUNCH("vq_nearest");
+        return BBDM_OK;
+    }, one_of<1, 2, 3, 4, 5, 6, 7, 8>(e_dim));
 }

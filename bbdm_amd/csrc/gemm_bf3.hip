@@ -23,6 +23,7 @@
 //  * Lane l supplies row (l & 31) and the 8 consecutive k of half (l >> 5) for A and for B alike (the sum over k does not
 //    depend on which k a lane carries as long as A and B agree); C/D layout = the f32 32x32 layout (cdna_hip_programming.md).
 #include "bf3_split.h"
+#include "dispatch.h"
 #include <stdlib.h>
 
 namespace {
@@ -264,26 +265,6 @@ extern "C" int bbdm_gemm_bf3_supported(long long T, int CinPad, int Cout) {
            (size_t)T * (size_t)CinPad < (1ull << 32);
 }
 
-template <bool RES>
-static int bf3_launch(const Bf3Args& a, long long blocks, int batch, hipStream_t st) {
-    static bool attr_set_dev[BBDM_MAX_DEVICES] = {};
-    bool& attr_set = attr_set_dev[bbdm_device_slot()];
-    const size_t lds = 2 * STAGE;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<RES>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) {
-            bbdm_set_error("gemm_bf3: hipFuncSetAttribute(%zu B LDS) failed", lds);
-            return BBDM_E_LAUNCH;
-        }
-        attr_set = true;
-    }
-    if (a.by_batch)
-        hipLaunchKernelGGL((gemm_bf3_kernel<RES>), dim3((unsigned)(8 * blocks * ((batch + 7) / 8))), dim3(NTHR), lds, st, a);
-    else
-        hipLaunchKernelGGL((gemm_bf3_kernel<RES>), dim3((unsigned)blocks, 1, batch), dim3(NTHR), lds, st, a);
-    return BBDM_OK;
-}
-
 static int bf3_run(Bf3Args& a, int batch, hipStream_t st) {
     a.CoutPad = cdiv(a.Cout, 128) * 128;
     a.nchunks = a.Cin / KC;
@@ -295,10 +276,14 @@ static int bf3_run(Bf3Args& a, int batch, hipStream_t st) {
     a.tiles = (int)blocks;
     a.batch = batch;
     a.by_batch = (by_batch_env && batch >= 8 && (batch % 8 == 0 || by_batch_env == 2)) ? 1 : 0;
-    const int rc = a.res ? bf3_launch<true>(a, blocks, batch, st) : bf3_launch<false>(a, blocks, batch, st);
-    if (rc != BBDM_OK) return rc;
-    BBDM_CHECK_LAUNCH("gemm_bf3");
-    return BBDM_OK;
+    const dim3 g = a.by_batch ? dim3((unsigned)(8 * blocks * ((batch + 7) / 8))) : dim3((unsigned)blocks, 1, batch);
+    return dispatch([&](auto RES) {
+        const size_t lds = 2 * STAGE;
+        if (const int rc = bbdm_ensure_lds<gemm_bf3_kernel<RES()>>(lds, "gemm_bf3")) return rc;
+        hipLaunchKernelGGL((gemm_bf3_kernel<RES()>), g, dim3(NTHR), lds, st, a);
+        BBDM_CHECK_LAUNCH("gemm_bf3");
+        return BBDM_OK;
+    }, a.res != nullptr);
 }
 
 extern "C" int bbdm_gemm_bf3_f32(const float* V, const void* packed_bf3, float* M, int batch, long long T, int CinPad, int Cout,

@@ -29,6 +29,7 @@
 // both operands by LDS-DMA two steps ahead, fp32 A split at the fragment read: round 4); the NS = 3 build of the pipe kernel for
 // small launches whose workgroups have a CU to themselves (round 4).
 #include "bf3_split.h"
+#include "dispatch.h"
 #include "h2_split.h"
 #include "lds_dma.h"
 #include <stdlib.h>
@@ -1015,19 +1016,10 @@ static inline long long by_batch_slots(long long blocks, int batch) {
 }
 template <int WM, int WN, bool RES, int NS = 2, int NP = 3>
 static int bf3p_launch(Bf3pArgs& a, int batch, hipStream_t st) {
-    static bool attr_set_dev[BBDM_MAX_DEVICES] = {};
-    bool& attr_set = attr_set_dev[bbdm_device_slot()];
     // the fp16-pair kernel on 256 x 256 tiles: the four-slot ring (one workgroup per CU either way; 128 of the 160 KB)
     constexpr bool R4 = NP == 2 && NS == 2 && WM == 4 && WN == 4;
     const size_t lds = (R4 ? 4 : NS) * (size_t)(WM * 2 * NP + WN * 2 * NP) * UNIT;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3p_pipe_kernel<WM, WN, RES, NS, NP, R4>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            bbdm_set_error("gemm_bf3p: hipFuncSetAttribute(%zu B LDS) failed", lds);
-            return BBDM_E_LAUNCH;
-        }
-        attr_set = true;
-    }
+    if (const int rc = bbdm_ensure_lds<gemm_bf3p_pipe_kernel<WM, WN, RES, NS, NP, R4>>(lds, "gemm_bf3p")) return rc;
     const long long blocks = (((long long)a.T + WM * 64 - 1) / (WM * 64)) * (a.tilesN * 2 / WN);     // (the last row tile may be ragged)
     BBDM_REQUIRE(blocks * ((batch + 7) / 8) * 8 < (1ll << 31), "gemm_bf3p: too many tiles");
     a.tiles = (int)blocks;
@@ -1126,12 +1118,12 @@ int bf3p_forward(const void* a_planes, const void* b_planes, const float* bias, 
     const int small_wg = 200;
     auto wgs = [&](int bm, int bn) { return (long long)nb * cdiv((int)rows, bm) * cdiv(CoutPad, bn); };
     int rc;
-#define BBDM_BF3P_GO_NS(WM, WN, NS)                                                                                        \
-    (np == 3 ? (residual ? bf3p_launch<WM, WN, true, NS, 3>(a, nb, st) : bf3p_launch<WM, WN, false, NS, 3>(a, nb, st))     \
-             : (residual ? bf3p_launch<WM, WN, true, NS, 2>(a, nb, st) : bf3p_launch<WM, WN, false, NS, 2>(a, nb, st)))
-#define BBDM_BF3P_GO(WM, WN) BBDM_BF3P_GO_NS(WM, WN, 2)
-    if (g_bf3p_variant == 4) rc = wide ? BBDM_BF3P_GO(4, 4) : BBDM_BF3P_GO(4, 2);
-    else if (g_bf3p_variant == 5) rc = BBDM_BF3P_GO(4, 2);
+    auto go = [&](auto WM, auto WN, auto NS) {      // the wave tile and the LDS stages are the branches' choice, below
+        return dispatch([&](auto NP, auto RES) { return bf3p_launch<WM(), WN(), RES(), NS(), NP()>(a, nb, st); }, one_of<3, 2>(np),
+                        residual != nullptr);
+    };
+    if (g_bf3p_variant == 4) rc = wide ? go(int_c<4>, int_c<4>, int_c<2>) : go(int_c<4>, int_c<2>, int_c<2>);
+    else if (g_bf3p_variant == 5) rc = go(int_c<4>, int_c<2>, int_c<2>);
     else if (g_bf3p_variant == 7 || wgs(256, 128) < small_wg || rows <= 128) {        // (<= 128 rows: a 256-row tile would be half padding)
         // LDS stages of the 128 x 128 kernel: three when every workgroup of the launch gets a CU to itself -- nobody else's copies cover
         // the wait for its own, and two stages expose an HBM round trip per chunk (measured per layer, profiles/r04_small_gemm_ring.md:
@@ -1140,8 +1132,8 @@ int bf3p_forward(const void* a_planes, const void* b_planes, const float* bias, 
         // and five stages never beat three.
         const int max_stages = 3;
         const long long w = (long long)cdiv((int)rows, 128) * cdiv(CoutPad, 128) * (a.by_batch ? (nb + 7) / 8 * 8 : nb);
-        if (max_stages >= 3 && a.nchunks / splits >= 8 && w <= bbdm_device_cus()) rc = BBDM_BF3P_GO_NS(2, 2, 3);
-        else rc = BBDM_BF3P_GO(2, 2);
+        if (max_stages >= 3 && a.nchunks / splits >= 8 && w <= bbdm_device_cus()) rc = go(int_c<2>, int_c<2>, int_c<3>);
+        else rc = go(int_c<2>, int_c<2>, int_c<2>);
     }
     else {
         // 256 x 256 (one workgroup per CU) vs 256 x 128 (two per CU): the CU that gets the most workgroups sets the time.  Mid-size
@@ -1153,10 +1145,8 @@ int bf3p_forward(const void* a_planes, const void* b_planes, const float* bias, 
             return a.by_batch ? (double)((by_batch_slots(per_entry, nb) + 31) / 32) : (double)((per_entry * nb + 255) / 256);
         };
         const double t44 = wide ? rounds(256, 256) : 1e30, t42 = rounds(256, 128) * 0.5 / 0.94;
-        rc = t44 <= t42 ? BBDM_BF3P_GO(4, 4) : BBDM_BF3P_GO(4, 2);
+        rc = t44 <= t42 ? go(int_c<4>, int_c<4>, int_c<2>) : go(int_c<4>, int_c<2>, int_c<2>);
     }
-#undef BBDM_BF3P_GO_NS
-#undef BBDM_BF3P_GO
     if (rc != BBDM_OK) return rc;
     BBDM_CHECK_LAUNCH("gemm_bf3p");
     return BBDM_OK;
@@ -1412,9 +1402,8 @@ int bf3p_tn(const void* at_planes, const void* bt_planes, float* C, int batch, l
     a.batch = nb;
     a.by_batch = (by_batch_env && nb >= 8) ? 1 : 0;              // (the pipe kernel returns early for the padding entries of a batch % 8 != 0)
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (np == 3) rc = sp.wn == 4 ? bf3p_launch<4, 4, false>(a, nb, st) : bf3p_launch<4, 2, false>(a, nb, st);
-    else rc = sp.wn == 4 ? bf3p_launch<4, 4, false, 2, 2>(a, nb, st) : bf3p_launch<4, 2, false, 2, 2>(a, nb, st);
+    const int rc = dispatch([&](auto WN, auto NP) { return bf3p_launch<4, WN(), false, 2, NP()>(a, nb, st); }, one_of<4, 2>(sp.wn),
+                            one_of<3, 2>(np));
     if (rc != BBDM_OK) return rc;
     BBDM_CHECK_LAUNCH("gemm_bf3p_tn");
     return BBDM_OK;
@@ -1443,17 +1432,8 @@ extern "C" int bbdm_gemm_h2p_tn_f32(const void* at_planes, const void* bt_planes
 namespace {
 template <int WM, int WN, bool RES, int NP = 3>
 int bf3q_launch(Bf3pArgs& a, const float* Af, int lda, int batch, hipStream_t st) {
-    static bool attr_set_dev[BBDM_MAX_DEVICES] = {};
-    bool& attr_set = attr_set_dev[bbdm_device_slot()];
     const size_t lds = 2 * (size_t)(WM * 2 * NP + WN * 2 * NP) * UNIT;
-    const void* fn = reinterpret_cast<const void*>(gemm_bf3q_pipe_kernel<WM, WN, RES, NP>);
-    if (!attr_set) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            bbdm_set_error("gemm_bf3q: hipFuncSetAttribute(%zu B LDS) failed", lds);
-            return BBDM_E_LAUNCH;
-        }
-        attr_set = true;
-    }
+    if (const int rc = bbdm_ensure_lds<gemm_bf3q_pipe_kernel<WM, WN, RES, NP>>(lds, "gemm_bf3q")) return rc;
     const long long blocks = (((long long)a.T + WM * 64 - 1) / (WM * 64)) * (a.tilesN * 2 / WN);
     BBDM_REQUIRE(blocks * ((batch + 7) / 8) * 8 < (1ll << 31), "gemm_bf3q: too many tiles");
     a.tiles = (int)blocks;
@@ -1486,9 +1466,8 @@ extern "C" int bbdm_conv1x1_bf3q_f32(const float* x, int ldx, const void* b_plan
     a.ldo = ldo; a.ldr = ldr; a.bias = bias; a.res = residual;
     a.ksplits = 1; a.kps = a.nchunks; a.P = 1; a.batch = 1; a.by_batch = 0;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (CoutPad % 256 == 0) rc = residual ? bf3q_launch<3, 4, true>(a, x, ldx, 1, st) : bf3q_launch<3, 4, false>(a, x, ldx, 1, st);
-    else rc = residual ? bf3q_launch<3, 2, true>(a, x, ldx, 1, st) : bf3q_launch<3, 2, false>(a, x, ldx, 1, st);
+    const int rc = dispatch([&](auto WN, auto RES) { return bf3q_launch<3, WN(), RES()>(a, x, ldx, 1, st); },
+                            one_of<4, 2>(CoutPad % 256 == 0 ? 4 : 2), residual != nullptr);
     if (rc != BBDM_OK) return rc;
     BBDM_CHECK_LAUNCH("conv1x1_bf3q");
     return BBDM_OK;
@@ -1516,9 +1495,8 @@ extern "C" int bbdm_conv1x1_h2q_f32(const float* x, int ldx, const void* b_plane
     a.ksplits = 1; a.kps = a.nchunks; a.P = 1; a.batch = 1; a.by_batch = 0;
     a.hA = xbound; a.hB = wbound; a.gA = 1.f;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (CoutPad % 256 == 0) rc = residual ? bf3q_launch<4, 4, true, 2>(a, x, ldx, 1, st) : bf3q_launch<4, 4, false, 2>(a, x, ldx, 1, st);
-    else rc = residual ? bf3q_launch<4, 2, true, 2>(a, x, ldx, 1, st) : bf3q_launch<4, 2, false, 2>(a, x, ldx, 1, st);
+    const int rc = dispatch([&](auto WN, auto RES) { return bf3q_launch<4, WN(), RES(), 2>(a, x, ldx, 1, st); },
+                            one_of<4, 2>(CoutPad % 256 == 0 ? 4 : 2), residual != nullptr);
     if (rc != BBDM_OK) return rc;
     BBDM_CHECK_LAUNCH("conv1x1_h2q");
     return BBDM_OK;
@@ -1551,23 +1529,14 @@ int conv1x1_small(const float* x, int ldx, const void* b_planes, const float* bi
     constexpr int NS = 3;      // (four stages = all 160 KB of LDS, measured: no faster -- the chain is bound by what one CU's LDS-DMA path moves,
                                // ~40 GB/s, not by the distance of the prefetch: profiles/r04_small_1x1.md)
     const size_t lds = NS * (size_t)(64 * 64 * 4 + 2 * 4 * NP * UNIT);
-    static bool attr_set_dev[BBDM_MAX_DEVICES][2] = {};
-    bool& attr_set = attr_set_dev[bbdm_device_slot()][residual ? 1 : 0];
-    if (!attr_set) {
-        const void* fn = residual ? reinterpret_cast<const void*>(gemm_bf3s_kernel<true, NS, NP>) : reinterpret_cast<const void*>(gemm_bf3s_kernel<false, NS, NP>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            bbdm_set_error("conv1x1_bf3s: hipFuncSetAttribute(%zu B LDS) failed", lds);
-            return BBDM_E_LAUNCH;
-        }
-        attr_set = true;
-    }
-    BBDM_REQUIRE((long long)tilesM * tilesN < (1ll << 31), "conv1x1_bf3s: too many tiles");
-    const dim3 grid((unsigned)(tilesM * tilesN));
-    hipStream_t st = (hipStream_t)stream;
-    if (residual) hipLaunchKernelGGL((gemm_bf3s_kernel<true, NS, NP>), grid, dim3(256), lds, st, a, x, ldx);
-    else hipLaunchKernelGGL((gemm_bf3s_kernel<false, NS, NP>), grid, dim3(256), lds, st, a, x, ldx);
-    BBDM_CHECK_LAUNCH("conv1x1_bf3s");
-    return BBDM_OK;
+    return dispatch([&](auto RES) {
+        if (const int rc = bbdm_ensure_lds<gemm_bf3s_kernel<RES(), NS, NP>>(lds, "conv1x1_bf3s")) return rc;
+        BBDM_REQUIRE((long long)tilesM * tilesN < (1ll << 31), "conv1x1_bf3s: too many tiles");
+        const dim3 grid((unsigned)(tilesM * tilesN));
+        hipLaunchKernelGGL((gemm_bf3s_kernel<RES(), NS, NP>), grid, dim3(256), lds, (hipStream_t)stream, a, x, ldx);
+        BBDM_CHECK_LAUNCH("conv1x1_bf3s");
+        return BBDM_OK;
+    }, residual != nullptr);
 }
 }  // namespace
 

@@ -19,6 +19,7 @@
 // than m = 4 per layer where the image is >= 64 pixels a side (little edge waste) and there are >= ~1000 tiles; slower
 // on 16x16 / 32x32 latents, where m = 4 stays (bbdm_amd/unet.py: winograd_tile).
 #include "winograd_math.h"
+#include "dispatch.h"
 #include <stdlib.h>
 #include "bf3_split.h"
 #include "h2_split.h"
@@ -1094,23 +1095,16 @@ extern "C" int bbdm_winograd_pack_weight_f32(int m, const float* w_oihw, float* 
     const size_t per = (size_t)nchunks * CoutPad * KC;
     int blocks = (int)((per + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    if (m == 7)
-        hipLaunchKernelGGL(winograd_weight72_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, packed, Cout, Cin,
-                           CoutPad, nchunks);
-    else if (m == 2)
-        hipLaunchKernelGGL(winograd_weight_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, packed, Cout,
-                           Cin, CoutPad, nchunks, dgrad);
-    else if (m == 4)
-        hipLaunchKernelGGL(winograd_weight_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, packed, Cout,
-                           Cin, CoutPad, nchunks, dgrad);
-    else if (m == 8)
-        hipLaunchKernelGGL(winograd_weight_kernel<8>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, packed, Cout,
-                           Cin, CoutPad, nchunks, dgrad);
-    else
-        hipLaunchKernelGGL(winograd_weight_kernel<6>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, packed, Cout,
-                           Cin, CoutPad, nchunks, dgrad);
-    BBDM_CHECK_LAUNCH("winograd_pack");
-    return BBDM_OK;
+    return dispatch([&](auto MO) {
+        if constexpr (MO() == 7)
+            hipLaunchKernelGGL(winograd_weight72_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, packed, Cout, Cin,
+                               CoutPad, nchunks);
+        else
+            hipLaunchKernelGGL(winograd_weight_kernel<MO()>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, packed, Cout,
+                               Cin, CoutPad, nchunks, dgrad);
+        BBDM_CHECK_LAUNCH("winograd_pack");
+        return BBDM_OK;
+    }, one_of<7, 2, 4, 8, 6>(m));
 }
 
 // ... with the B planes of gemm_bf3p.hip as the destination (= bbdm_winograd_pack_weight_f32 + bbdm_gemm_bf3p_pack_b_f32 up to FMA contraction;
@@ -1127,19 +1121,12 @@ static int winograd_pack_planes(int m, const float* w_oihw, void* b_planes, int 
     int blocks = (int)((pairs + 255) / 256);
     if (blocks > 8192) blocks = 8192;
     unsigned char* d = (unsigned char*)b_planes;
-#define BBDM_WINO_PK(MO)                                                                                                          \
-    do {                                                                                                                          \
-        if (wbound)                                                                                                               \
-            hipLaunchKernelGGL((winograd_weight_planes_kernel<MO, 2>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, d, Cout, \
-                               Cin, CoutPad, nchunks, dgrad, wbound);                                                             \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((winograd_weight_planes_kernel<MO, 3>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, d, Cout, \
-                               Cin, CoutPad, nchunks, dgrad, nullptr);                                                            \
-    } while (0)
-    if (m == 2) BBDM_WINO_PK(2); else if (m == 4) BBDM_WINO_PK(4); else if (m == 8) BBDM_WINO_PK(8); else BBDM_WINO_PK(6);
-#undef BBDM_WINO_PK
-    BBDM_CHECK_LAUNCH("winograd_pack_planes");
-    return BBDM_OK;
+    return dispatch([&](auto MO, auto NPL) {       // two planes (the fp16 pair) under wbound, three (bf16x3) without
+        hipLaunchKernelGGL((winograd_weight_planes_kernel<MO(), NPL()>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, d, Cout,
+                           Cin, CoutPad, nchunks, dgrad, wbound);
+        BBDM_CHECK_LAUNCH("winograd_pack_planes");
+        return BBDM_OK;
+    }, one_of<2, 4, 8, 6>(m), one_of<2, 3>(wbound ? 2 : 3));
 }
 extern "C" int bbdm_winograd_pack_weight_bf3p_f32(int m, const float* w_oihw, void* b_planes, int Cout, int Cin, int InPad, int dgrad,
                                                   void* stream) {
@@ -1192,29 +1179,16 @@ extern "C" int bbdm_winograd_input_f32(int m, const float* x, int ldx, float* V,
     if (blocks > 16384) blocks = 16384;
     const dim3 g((unsigned)blocks), b(256);
     hipStream_t st = (hipStream_t)stream;
-    if (m == 6) {
-#define BBDM_WINO_IN6(PRE, UP)                                                                                            \
-    hipLaunchKernelGGL((winograd_input6_kernel<PRE, UP>), g, b, 0, st, x, ldx, V, pre_scale, pre_bias, pre_ld, pre_silu, N, \
-                       H, W, CinPad, vplane)
-        if (pre_scale) { if (upsample) BBDM_WINO_IN6(true, true); else BBDM_WINO_IN6(true, false); }
-        else           { if (upsample) BBDM_WINO_IN6(false, true); else BBDM_WINO_IN6(false, false); }
-#undef BBDM_WINO_IN6
+    return dispatch([&](auto MO, auto PRE, auto UP) {
+        if constexpr (MO() == 6)
+            hipLaunchKernelGGL((winograd_input6_kernel<PRE(), UP()>), g, b, 0, st, x, ldx, V, pre_scale, pre_bias, pre_ld, pre_silu, N,
+                               H, W, CinPad, vplane);
+        else
+            hipLaunchKernelGGL((winograd_input_kernel<MO(), PRE(), UP()>), g, b, 0, st, x, ldx, V, pre_scale, pre_bias, pre_ld, pre_silu,
+                               N, H, W, CinPad, vplane);
         BBDM_CHECK_LAUNCH("winograd_input");
         return BBDM_OK;
-    }
-#define BBDM_WINO_IN(MO, PRE, UP)                                                                                         \
-    hipLaunchKernelGGL((winograd_input_kernel<MO, PRE, UP>), g, b, 0, st, x, ldx, V, pre_scale, pre_bias, pre_ld, pre_silu, \
-                       N, H, W, CinPad, vplane)
-#define BBDM_WINO_IN_M(MO)                                                                      \
-    do {                                                                                        \
-        if (pre_scale) { if (upsample) BBDM_WINO_IN(MO, true, true); else BBDM_WINO_IN(MO, true, false); }   \
-        else           { if (upsample) BBDM_WINO_IN(MO, false, true); else BBDM_WINO_IN(MO, false, false); } \
-    } while (0)
-    if (m == 2) BBDM_WINO_IN_M(2); else BBDM_WINO_IN_M(4);
-#undef BBDM_WINO_IN_M
-#undef BBDM_WINO_IN
-    BBDM_CHECK_LAUNCH("winograd_input");
-    return BBDM_OK;
+    }, one_of<6, 2, 4>(m), pre_scale != nullptr, upsample != 0);      // (m = 8 takes whole 32-channel chunks: the branch above)
 }
 
 extern "C" int bbdm_winograd_gemm_f32(int m, const float* V, const float* packed_wino, float* M, int N, int H, int W,
@@ -1260,132 +1234,64 @@ static int winograd_input_planes(int m, const float* x, int ldx, void* Vp, void*
     BBDM_REQUIRE(!pre_scale || (pre_ld % 2 == 0 && pre_ld >= CinPad && (((uintptr_t)pre_scale | (uintptr_t)pre_bias) & 7) == 0),
                  "winograd_input_bf3p: pre_ld / alignment of the fused-producer coefficients");
     const size_t T = tiles_raw(N, H, W, m), Tp = tiles_padded(N, H, W, m);
-    const int nchunks = CinPad / KC, TG = (int)(Tp / 8);
+    int nchunks = CinPad / KC, TG = (int)(Tp / 8);
     const size_t plane = Tp * (size_t)CinPad * (f32out || hbound ? 4 : 6);  // bytes of one transform point
     const size_t plane_t = (size_t)((CinPad + 31) / 32 * 32) * Tp * (vt_h2 ? 4 : 6);       // ... of the transposed copy (whole 32-channel row groups)
     BBDM_REQUIRE(!Vt || (!upsample && ((uintptr_t)Vt & 15) == 0), "winograd_input_bf3p: the transposed copy needs upsample = 0, 16-B alignment");
     hipStream_t st = (hipStream_t)stream;
-    {
-        const long long blocks = 8ll * ((TG + 7) / 8) * nchunks;
-        BBDM_REQUIRE(blocks < (1ll << 31) && Tp < (1ull << 31), "winograd_input_bf3p: too many workgroups / tiles");
-        const dim3 g((unsigned)blocks);
-        const int Hs = upsample ? H / 2 : H, Ws = upsample ? W / 2 : W;
-        // 32-bit element indices + 24-bit row multiplies where the tensor allows it (every shape of the reference's templates)
-        // (option wino_idx64 = 1 forces the 64-bit variant: the tests run both on ordinary shapes)
-        const int idx64_env = bbdm_option(BBDM_OPT_WINO_IDX64);
-        const bool idx64 = idx64_env || (unsigned long long)N * Hs * Ws * (unsigned long long)ldx >= (1ull << 32) ||
-                           (unsigned long long)Ws * (unsigned long long)ldx >= (1ull << 24) || Hs >= (1 << 24);
-        const FastDiv dTW = fastdiv_make((unsigned)wino_tdim(W, m)), dTH = fastdiv_make((unsigned)wino_tdim(H, m)),
-                      dCH = fastdiv_make((unsigned)nchunks);
-        const GnFold gn = fold ? *fold : GnFold{};
-        if (m == 7) {                     // F(7x7, 2x2): the m = 6 kernel with windows 7 pixels apart
-#define BBDM_WINO_INS2_7(PRE, I64)                                                                                                \
-    hipLaunchKernelGGL((winograd_input_split2_kernel<6, PRE, false, false, I64, false, false, 7>), g, dim3(8 * 64), 0, st, x, ldx,   \
-                       (unsigned char*)Vp, pre_scale, pre_bias, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane, nullptr,  \
-                       plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2)
-#define BBDM_WINO_INS2_7H(PRE, I64)                                                                                               \
-    hipLaunchKernelGGL((winograd_input_split2_kernel<6, PRE, false, false, I64, false, false, 7, 2>), g, dim3(8 * 64), 0, st, x, ldx, \
-                       (unsigned char*)Vp, pre_scale, pre_bias, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane, nullptr,  \
-                       plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2)
-            if (hbound) {
-                if (pre_scale) { if (idx64) BBDM_WINO_INS2_7H(true, true); else BBDM_WINO_INS2_7H(true, false); }
-                else           { if (idx64) BBDM_WINO_INS2_7H(false, true); else BBDM_WINO_INS2_7H(false, false); }
-            }
-            else if (pre_scale) { if (idx64) BBDM_WINO_INS2_7(true, true); else BBDM_WINO_INS2_7(true, false); }
-            else           { if (idx64) BBDM_WINO_INS2_7(false, true); else BBDM_WINO_INS2_7(false, false); }
-#undef BBDM_WINO_INS2_7H
-#undef BBDM_WINO_INS2_7
-            BBDM_CHECK_LAUNCH("winograd_input_bf3p(m = 7)");
-            return BBDM_OK;
-        }
-        if (fold) {                       // the kernel forms the coefficients (small problems; 32-bit indices, no transposed copy)
-            BBDM_REQUIRE(!idx64 && !Vt, "winograd_input_bf3p_gn: tensor too large for the coefficient-folding variant");
-#define BBDM_WINO_INS2_G(MO)                                                                                                      \
-    do {                                                                                                                          \
-        if (upsample)                                                                                                             \
-            hipLaunchKernelGGL((winograd_input_split2_kernel<MO, true, true, false, false, true>), g, dim3((MO + 2) * 64), 0, st, x, ldx, \
-                               (unsigned char*)Vp, nullptr, nullptr, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane,  \
-                               nullptr, plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2);                                              \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((winograd_input_split2_kernel<MO, true, false, false, false, true>), g, dim3((MO + 2) * 64), 0, st, x, ldx, \
-                               (unsigned char*)Vp, nullptr, nullptr, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane,  \
-                               nullptr, plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2);                                              \
-    } while (0)
-#define BBDM_WINO_INS2_GH(MO)                                                                                                     \
-    do {                                                                                                                          \
-        if (upsample)                                                                                                             \
-            hipLaunchKernelGGL((winograd_input_split2_kernel<MO, true, true, false, false, true, false, MO, 2>), g, dim3((MO + 2) * 64), 0, st, x, ldx, \
-                               (unsigned char*)Vp, nullptr, nullptr, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane,  \
-                               nullptr, plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2);                                      \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((winograd_input_split2_kernel<MO, true, false, false, false, true, false, MO, 2>), g, dim3((MO + 2) * 64), 0, st, x, ldx, \
-                               (unsigned char*)Vp, nullptr, nullptr, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane,  \
-                               nullptr, plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2);                                      \
-    } while (0)
-            if (hbound) { if (m == 2) BBDM_WINO_INS2_GH(2); else if (m == 4) BBDM_WINO_INS2_GH(4); else BBDM_WINO_INS2_GH(6); }
-            else if (m == 2) BBDM_WINO_INS2_G(2); else if (m == 4) BBDM_WINO_INS2_G(4); else BBDM_WINO_INS2_G(6);
-#undef BBDM_WINO_INS2_GH
-#undef BBDM_WINO_INS2_G
-            BBDM_CHECK_LAUNCH("winograd_input_bf3p_gn");
-            return BBDM_OK;
-        }
-        if (f32out) {                     // fp32 rows instead of planes (no transposed copy, no coefficient folding)
-            BBDM_REQUIRE(!Vt && CinPad % 32 == 0, "winograd_input: the fp32 form has no transposed copy and takes whole 32-channel chunks");
-            // its workgroups own 4 tiles x 32 channels: re-derive the grid quantities the kernel reads
-            const int nchunks = CinPad / 32, TG = (int)(Tp / 4);
-            const FastDiv dCH = fastdiv_make((unsigned)nchunks);
-            const dim3 g((unsigned)(8ll * ((TG + 7) / 8) * nchunks));
-            BBDM_REQUIRE(8ll * ((TG + 7) / 8) * nchunks < (1ll << 31), "winograd_input: too many workgroups");
-#define BBDM_WINO_INS2_F(MO, PRE, UP, I64)                                                                                        \
-    hipLaunchKernelGGL((winograd_input_split2_kernel<MO, PRE, UP, false, I64, false, true>), g, dim3((MO + 2) * 64), 0, st, x, ldx, \
-                       (unsigned char*)Vp, pre_scale, pre_bias, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane, nullptr, \
-                       plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2)
-#define BBDM_WINO_INS2_FI(MO, PRE, UP) do { if (idx64) BBDM_WINO_INS2_F(MO, PRE, UP, true); else BBDM_WINO_INS2_F(MO, PRE, UP, false); } while (0)
-#define BBDM_WINO_INS2_FM(MO)                                                                                                     \
-    do {                                                                                                                          \
-        if (pre_scale) { if (upsample) BBDM_WINO_INS2_FI(MO, true, true); else BBDM_WINO_INS2_FI(MO, true, false); }              \
-        else           { if (upsample) BBDM_WINO_INS2_FI(MO, false, true); else BBDM_WINO_INS2_FI(MO, false, false); }            \
-    } while (0)
-            if (m == 2) BBDM_WINO_INS2_FM(2); else if (m == 4) BBDM_WINO_INS2_FM(4); else if (m == 8) BBDM_WINO_INS2_FM(8); else BBDM_WINO_INS2_FM(6);
-#undef BBDM_WINO_INS2_FM
-#undef BBDM_WINO_INS2_FI
-#undef BBDM_WINO_INS2_F
-            BBDM_CHECK_LAUNCH("winograd_input(fp32 rows, two-phase)");
-            return BBDM_OK;
-        }
-#define BBDM_WINO_INS2_I(MO, PRE, UP, TR, I64)                                                                                    \
-    hipLaunchKernelGGL((winograd_input_split2_kernel<MO, PRE, UP, TR, I64>), g, dim3((MO + 2) * 64), 0, st, x, ldx, (unsigned char*)Vp, \
-                       pre_scale, pre_bias, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane, (unsigned char*)Vt,   \
-                       plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2)
-#define BBDM_WINO_INS2(MO, PRE, UP, TR) do { if (idx64) BBDM_WINO_INS2_I(MO, PRE, UP, TR, true); else BBDM_WINO_INS2_I(MO, PRE, UP, TR, false); } while (0)
-#define BBDM_WINO_INS2_M(MO)                                                                        \
-    do {                                                                                            \
-        if (Vt) { if (pre_scale) BBDM_WINO_INS2(MO, true, false, true); else BBDM_WINO_INS2(MO, false, false, true); }   \
-        else if (pre_scale) { if (upsample) BBDM_WINO_INS2(MO, true, true, false); else BBDM_WINO_INS2(MO, true, false, false); }   \
-        else           { if (upsample) BBDM_WINO_INS2(MO, false, true, false); else BBDM_WINO_INS2(MO, false, false, false); } \
-    } while (0)
-#define BBDM_WINO_INS2_HI(MO, PRE, UP, TR, I64)                                                                                   \
-    hipLaunchKernelGGL((winograd_input_split2_kernel<MO, PRE, UP, TR, I64, false, false, MO, 2>), g, dim3((MO + 2) * 64), 0, st, x, ldx, \
-                       (unsigned char*)Vp, pre_scale, pre_bias, pre_ld, pre_silu, N, H, W, nchunks, (unsigned)T, TG, plane,           \
-                       (unsigned char*)Vt, plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn, hbound, vt_h2)
-#define BBDM_WINO_INS2_H(MO, PRE, UP, TR) do { if (idx64) BBDM_WINO_INS2_HI(MO, PRE, UP, TR, true); else BBDM_WINO_INS2_HI(MO, PRE, UP, TR, false); } while (0)
-#define BBDM_WINO_INS2_HM(MO)                                                                       \
-    do {                                                                                            \
-        if (Vt) { if (pre_scale) BBDM_WINO_INS2_H(MO, true, false, true); else BBDM_WINO_INS2_H(MO, false, false, true); }   \
-        else if (pre_scale) { if (upsample) BBDM_WINO_INS2_H(MO, true, true, false); else BBDM_WINO_INS2_H(MO, true, false, false); }   \
-        else           { if (upsample) BBDM_WINO_INS2_H(MO, false, true, false); else BBDM_WINO_INS2_H(MO, false, false, false); } \
-    } while (0)
-        if (hbound) { if (m == 2) BBDM_WINO_INS2_HM(2); else if (m == 4) BBDM_WINO_INS2_HM(4); else if (m == 8) BBDM_WINO_INS2_HM(8); else BBDM_WINO_INS2_HM(6); }
-        else if (m == 2) BBDM_WINO_INS2_M(2); else if (m == 4) BBDM_WINO_INS2_M(4); else if (m == 8) BBDM_WINO_INS2_M(8); else BBDM_WINO_INS2_M(6);
-#undef BBDM_WINO_INS2_HM
-#undef BBDM_WINO_INS2_H
-#undef BBDM_WINO_INS2_HI
-#undef BBDM_WINO_INS2_M
-#undef BBDM_WINO_INS2
-#undef BBDM_WINO_INS2_I
-        BBDM_CHECK_LAUNCH("winograd_input_bf3p");
+    const long long blocks = 8ll * ((TG + 7) / 8) * nchunks;
+    BBDM_REQUIRE(blocks < (1ll << 31) && Tp < (1ull << 31), "winograd_input_bf3p: too many workgroups / tiles");
+    dim3 g((unsigned)blocks);
+    const int Hs = upsample ? H / 2 : H, Ws = upsample ? W / 2 : W;
+    // 32-bit element indices + 24-bit row multiplies where the tensor allows it (every shape of the reference's templates)
+    // (option wino_idx64 = 1 forces the 64-bit variant: the tests run both on ordinary shapes)
+    const int idx64_env = bbdm_option(BBDM_OPT_WINO_IDX64);
+    const bool idx64 = idx64_env || (unsigned long long)N * Hs * Ws * (unsigned long long)ldx >= (1ull << 32) ||
+                       (unsigned long long)Ws * (unsigned long long)ldx >= (1ull << 24) || Hs >= (1 << 24);
+    const FastDiv dTW = fastdiv_make((unsigned)wino_tdim(W, m)), dTH = fastdiv_make((unsigned)wino_tdim(H, m));
+    FastDiv dCH = fastdiv_make((unsigned)nchunks);
+    const GnFold gn = fold ? *fold : GnFold{};
+    // THE launch of winograd_input_split2_kernel; the forms below choose its template arguments (and only those they can reach: the
+    // transposed copy has no upsample, the coefficient fold is 32-bit with m <= 6, windows 7 apart exist for m = 6 alone).
+    // The kernel gets Vt only with TR and the caller's coefficients only without GNC, whatever the caller passed.
+    const char* what = "winograd_input_bf3p";
+    auto launch = [&](auto MO, auto PRE, auto UP, auto TR, auto I64, auto GNC, auto F32, auto ST, auto NPL) {
+        hipLaunchKernelGGL((winograd_input_split2_kernel<MO(), PRE(), UP(), TR(), I64(), GNC(), F32(), ST(), NPL()>), g, dim3((MO() + 2) * 64),
+                           0, st, x, ldx, (unsigned char*)Vp, GNC() ? nullptr : pre_scale, GNC() ? nullptr : pre_bias, pre_ld, pre_silu, N, H, W,
+                           nchunks, (unsigned)T, TG, plane, TR() ? (unsigned char*)Vt : nullptr, plane_t, (int)(Tp / 16), dTW, dTH, dCH, gn,
+                           hbound, vt_h2);
+        BBDM_CHECK_LAUNCH(what);
         return BBDM_OK;
+    };
+    const auto pre = pre_scale != nullptr, up = upsample != 0;
+    const auto npl = one_of<3, 2>(hbound ? 2 : 3);            // bf16x3 planes, or the fp16 pair under hbound
+    if (m == 7) {                         // F(7x7, 2x2): the m = 6 kernel with windows 7 pixels apart
+        what = "winograd_input_bf3p(m = 7)";
+        return dispatch([&](auto PRE, auto I64, auto NPL) { return launch(int_c<6>, PRE, no_tag, no_tag, I64, no_tag, no_tag, int_c<7>, NPL); },
+                        pre, idx64, npl);
     }
+    if (fold) {                           // the kernel forms the coefficients (small problems; 32-bit indices, no transposed copy)
+        BBDM_REQUIRE(!idx64 && !Vt, "winograd_input_bf3p_gn: tensor too large for the coefficient-folding variant");
+        what = "winograd_input_bf3p_gn";
+        return dispatch([&](auto MO, auto UP, auto NPL) { return launch(MO, yes_tag, UP, no_tag, no_tag, yes_tag, no_tag, MO, NPL); },
+                        one_of<2, 4, 6>(m), up, npl);
+    }
+    if (f32out) {                         // fp32 rows instead of planes (no transposed copy, no coefficient folding)
+        BBDM_REQUIRE(!Vt && CinPad % 32 == 0, "winograd_input: the fp32 form has no transposed copy and takes whole 32-channel chunks");
+        // its workgroups own 4 tiles x 32 channels: re-derive the grid quantities the kernel reads
+        nchunks = CinPad / 32, TG = (int)(Tp / 4);
+        dCH = fastdiv_make((unsigned)nchunks);
+        g = dim3((unsigned)(8ll * ((TG + 7) / 8) * nchunks));
+        BBDM_REQUIRE(8ll * ((TG + 7) / 8) * nchunks < (1ll << 31), "winograd_input: too many workgroups");
+        what = "winograd_input(fp32 rows, two-phase)";
+        return dispatch([&](auto MO, auto PRE, auto UP, auto I64) { return launch(MO, PRE, UP, no_tag, I64, no_tag, yes_tag, MO, int_c<3>); },
+                        one_of<2, 4, 8, 6>(m), pre, up, idx64);
+    }
+    if (Vt)
+        return dispatch([&](auto MO, auto PRE, auto I64, auto NPL) { return launch(MO, PRE, no_tag, yes_tag, I64, no_tag, no_tag, MO, NPL); },
+                        one_of<2, 4, 8, 6>(m), pre, idx64, npl);
+    return dispatch([&](auto MO, auto PRE, auto UP, auto I64, auto NPL) { return launch(MO, PRE, UP, no_tag, I64, no_tag, no_tag, MO, NPL); },
+                    one_of<2, 4, 8, 6>(m), pre, up, idx64, npl);
 }
 
 extern "C" int bbdm_winograd_input_bf3p_f32(int m, const float* x, int ldx, void* Vp, const float* pre_scale,
@@ -1401,20 +1307,26 @@ extern "C" int bbdm_winograd_input_bf3p_f32(int m, const float* x, int ldx, void
 // two.  For SMALL problems (every thread repeats the fp64 fold for its channel pair).  Argument order of bbdm_winograd_input_bf3p_f32
 // with (stats, unused) in place of (pre_scale, pre_bias) and C in place of pre_ld; the GroupNorm's parameters follow CinPad.
 // C == CinPad, C / G even, HW = pixels per image of the NORMALISED tensor (x's own H * W, also when upsample = 1).
+static int winograd_input_planes_gn(const char* name, bool h2, int m, const float* x, int ldx, void* Vp, const void* stats, int C, int pre_silu,
+                                    int upsample, int N, int H, int W, int CinPad, const float* gamma, const float* beta, const float* film,
+                                    int film_ld, int HW, int G, float eps, const float* vbound, void* stream) {
+    BBDM_REQUIRE(stats && gamma && beta && (!h2 || vbound), "%s: null pointer", name);
+    BBDM_REQUIRE(C == CinPad && G > 0 && C % G == 0 && (C / G) % 2 == 0 && HW > 0 && (!film || film_ld >= 2 * C),
+                 "%s: C=%d CinPad=%d G=%d HW=%d film_ld=%d", name, C, CinPad, G, HW, film_ld);
+    BBDM_REQUIRE((((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)film) & 7) == 0 && (!film || film_ld % 2 == 0),
+                 "%s: gamma / beta / film must be 8-byte aligned", name);
+    GnFold f;
+    f.stats = (const unsigned long long*)stats; f.gamma = gamma; f.beta = beta; f.film = film;
+    f.film_ld = film_ld; f.C = C; f.G = G; f.cpg = C / G; f.cnt = (double)HW * (double)(C / G); f.eps = eps;
+    return winograd_input_planes(m, x, ldx, Vp, nullptr, nullptr, nullptr, C, pre_silu, upsample, N, H, W, CinPad, stream, &f, false, vbound);
+}
 extern "C" int bbdm_winograd_input_bf3p_gn_f32(int m, const float* x, int ldx, void* Vp, const void* stats, const void* unused, int C,
                                                int pre_silu, int upsample, int N, int H, int W, int CinPad, const float* gamma,
                                                const float* beta, const float* film, int film_ld, int HW, int G, float eps,
                                                void* stream) {
     (void)unused;
-    BBDM_REQUIRE(stats && gamma && beta, "winograd_input_bf3p_gn: null pointer");
-    BBDM_REQUIRE(C == CinPad && G > 0 && C % G == 0 && (C / G) % 2 == 0 && HW > 0 && (!film || film_ld >= 2 * C),
-                 "winograd_input_bf3p_gn: C=%d CinPad=%d G=%d HW=%d film_ld=%d", C, CinPad, G, HW, film_ld);
-    BBDM_REQUIRE((((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)film) & 7) == 0 && (!film || film_ld % 2 == 0),
-                 "winograd_input_bf3p_gn: gamma / beta / film must be 8-byte aligned");
-    GnFold f;
-    f.stats = (const unsigned long long*)stats; f.gamma = gamma; f.beta = beta; f.film = film;
-    f.film_ld = film_ld; f.C = C; f.G = G; f.cpg = C / G; f.cnt = (double)HW * (double)(C / G); f.eps = eps;
-    return winograd_input_planes(m, x, ldx, Vp, nullptr, nullptr, nullptr, C, pre_silu, upsample, N, H, W, CinPad, stream, &f, false);
+    return winograd_input_planes_gn("winograd_input_bf3p_gn", false, m, x, ldx, Vp, stats, C, pre_silu, upsample, N, H, W, CinPad, gamma, beta,
+                                    film, film_ld, HW, G, eps, nullptr, stream);
 }
 
 // ... and, for the training forward, ALSO the transposed planes Vt (bbdm_gemm_bf3p_tn_at_bytes((m+2)^2, tiles, CinPad) bytes): the A
@@ -1459,15 +1371,8 @@ extern "C" int bbdm_winograd_input_h2p_gn_f32(int m, const float* x, int ldx, vo
                                               const float* beta, const float* film, int film_ld, int HW, int G, float eps,
                                               const float* vbound, void* stream) {
     (void)unused;
-    BBDM_REQUIRE(stats && gamma && beta && vbound, "winograd_input_h2p_gn: null pointer");
-    BBDM_REQUIRE(C == CinPad && G > 0 && C % G == 0 && (C / G) % 2 == 0 && HW > 0 && (!film || film_ld >= 2 * C),
-                 "winograd_input_h2p_gn: C=%d CinPad=%d G=%d HW=%d film_ld=%d", C, CinPad, G, HW, film_ld);
-    BBDM_REQUIRE((((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)film) & 7) == 0 && (!film || film_ld % 2 == 0),
-                 "winograd_input_h2p_gn: gamma / beta / film must be 8-byte aligned");
-    GnFold f;
-    f.stats = (const unsigned long long*)stats; f.gamma = gamma; f.beta = beta; f.film = film;
-    f.film_ld = film_ld; f.C = C; f.G = G; f.cpg = C / G; f.cnt = (double)HW * (double)(C / G); f.eps = eps;
-    return winograd_input_planes(m, x, ldx, Vp, nullptr, nullptr, nullptr, C, pre_silu, upsample, N, H, W, CinPad, stream, &f, false, vbound);
+    return winograd_input_planes_gn("winograd_input_h2p_gn", true, m, x, ldx, Vp, stats, C, pre_silu, upsample, N, H, W, CinPad, gamma, beta,
+                                    film, film_ld, HW, G, eps, vbound, stream);
 }
 extern "C" int bbdm_winograd_gemm_h2p_splitk_f32(int m, const void* Vp, const void* b_planes, float* M, int N, int H, int W, int CinPad,
                                                  int Cout, int splits, const float* vbound, const float* ubound, void* stream) {
@@ -1568,66 +1473,42 @@ extern "C" int bbdm_winograd_output_splitk_stats_f32(int m, const float* M, cons
         const long long per_image = (long long)wino_tdim(H, m) * wino_tdim(W, m);
         if (tpw > per_image) tpw = (int)per_image;
         if (tpw < 1) tpw = 1;
-        if (m == 7) {
-            if (tpw == 1)
-                hipLaunchKernelGGL((winograd_output_lds_kernel<7, false, 1, 8>), dim3((unsigned)(T * (size_t)(Cm / 128))), dim3(512), 0, s_, M,
-                                   Tp * (size_t)Cm, Cm, 1, bias, residual, ldr, rpi, out, ldo, N, H, W, Cout, Cm / 128, (long long)T, st, ph, 1);
-            else
-                hipLaunchKernelGGL((winograd_output_lds_kernel<7, false, 2, 8>), dim3((unsigned)(((T + tpw - 1) / tpw) * (size_t)(Cm / 128))),
-                                   dim3(512), 0, s_, M, Tp * (size_t)Cm, Cm, 1, bias, residual, ldr, rpi, out, ldo, N, H, W, Cout, Cm / 128,
-                                   (long long)T, st, ph, tpw);
-            BBDM_CHECK_LAUNCH("winograd_output(m = 7)");
+        // THE launch of the LDS kernel: AL = transform points per side (m = 7 runs on m = 6's eight), TPW = 1 only where an image has one tile
+        auto launch = [&](auto MO, auto RES, auto TPW, auto AL, size_t lds, const char* what) {
+            hipLaunchKernelGGL((winograd_output_lds_kernel<MO(), RES(), TPW(), AL()>), dim3((unsigned)(((T + tpw - 1) / tpw) * (size_t)(Cm / 128))),
+                               dim3(AL() * 64), lds, s_, M, Tp * (size_t)Cm, Cm, splits, bias, residual, ldr, rpi, out, ldo, N, H, W, Cout,
+                               Cm / 128, (long long)T, st, ph, tpw);
+            BBDM_CHECK_LAUNCH(what);
             return BBDM_OK;
-        }
-#define BBDM_WINO_OUT(MO_, RES_, TPW_)                                                                                              \
-    hipLaunchKernelGGL((winograd_output_lds_kernel<MO_, RES_, TPW_>), dim3((unsigned)(((T + tpw - 1) / tpw) * (size_t)(Cm / 128))), \
-                       dim3((MO_ + 2) * 64), 0, s_, M, Tp * (size_t)Cm, Cm, splits, bias, residual, ldr, rpi, out, ldo, N, H, W, Cout, \
-                       Cm / 128, (long long)T, st, ph, tpw)
-#define BBDM_WINO_OUT_M(MO_)                                                                                   \
-    do {                                                                                                       \
-        if (tpw == 1) { if (residual) BBDM_WINO_OUT(MO_, true, 1); else BBDM_WINO_OUT(MO_, false, 1); }        \
-        else { if (residual) BBDM_WINO_OUT(MO_, true, 2); else BBDM_WINO_OUT(MO_, false, 2); }                 \
-    } while (0)
+        };
+        const auto one_tile = one_of<1, 2>(tpw == 1 ? 1 : 2);
+        if (m == 7)                                   // (no residual, no split-K partials: checked above)
+            return dispatch([&](auto TPW) { return launch(int_c<7>, no_tag, TPW, int_c<8>, 0, "winograd_output(m = 7)"); }, one_tile);
         if (m == 8) {      // two buffers = 80 KB of (dynamic) LDS, two workgroups of ten waves per CU
             constexpr size_t lds8 = (size_t)2 * 8 * 10 * 64 * sizeof(float2);
-            static bool attr_set_dev[BBDM_MAX_DEVICES] = {};
-            bool& attr_set = attr_set_dev[bbdm_device_slot()];
-            if (!attr_set) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(winograd_output_lds_kernel<8, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(winograd_output_lds_kernel<8, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8) != hipSuccess) {
-                    bbdm_set_error("winograd_output: hipFuncSetAttribute(%zu B LDS) failed", lds8);
-                    return BBDM_E_LAUNCH;
-                }
-                attr_set = true;
-            }
             if (tpw < 2) tpw = per_image >= 2 ? 2 : 1;
-#define BBDM_WINO_OUT8(RES_)                                                                                                        \
-    hipLaunchKernelGGL((winograd_output_lds_kernel<8, RES_, 2>), dim3((unsigned)(((T + tpw - 1) / tpw) * (size_t)(Cm / 128))), dim3(640), \
-                       lds8, s_, M, Tp * (size_t)Cm, Cm, splits, bias, residual, ldr, rpi, out, ldo, N, H, W, Cout, Cm / 128, (long long)T, st, ph, tpw)
-            if (residual) BBDM_WINO_OUT8(true); else BBDM_WINO_OUT8(false);
-#undef BBDM_WINO_OUT8
+            return dispatch([&](auto RES) {
+                if (const int rc = bbdm_ensure_lds<winograd_output_lds_kernel<8, RES(), 2>>(lds8, "winograd_output")) return rc;
+                return launch(int_c<8>, RES, int_c<2>, int_c<10>, lds8, "winograd_output");
+            }, residual != nullptr);
         }
-        else if (m == 6) BBDM_WINO_OUT_M(6); else if (m == 4) BBDM_WINO_OUT_M(4); else BBDM_WINO_OUT_M(2);
-#undef BBDM_WINO_OUT_M
-#undef BBDM_WINO_OUT
-        BBDM_CHECK_LAUNCH("winograd_output");
-        return BBDM_OK;
+        return dispatch([&](auto MO, auto TPW, auto RES) { return launch(MO, RES, TPW, int_c<MO() + 2>, 0, "winograd_output"); },
+                        one_of<6, 4, 2>(m), one_tile, residual != nullptr);
     }
     BBDM_REQUIRE(m != 7 && m != 8, "winograd_output: m = 7 / 8 need Cout %% 128 == 0 (the two-phase kernel)");
-    if (m == 6 && residual)
-        hipLaunchKernelGGL(winograd_output6_kernel<true>, g, b, 0, s_, M, Tp * (size_t)Cm, Cm, bias, residual, ldr, rpi, out,
+    if (m == 6)
+        return dispatch([&](auto RES) {
+            hipLaunchKernelGGL(winograd_output6_kernel<RES()>, g, b, 0, s_, M, Tp * (size_t)Cm, Cm, bias, residual, ldr, rpi, out,
+                               ldo, N, H, W, Cout, (int)iters, st, ph);
+            BBDM_CHECK_LAUNCH("winograd_output");
+            return BBDM_OK;
+        }, residual != nullptr);
+    return dispatch([&](auto MO) {
+        hipLaunchKernelGGL(winograd_output_kernel<MO()>, g, b, 0, s_, M, Tp * (size_t)Cm, Cm, splits, bias, residual, ldr, rpi, out,
                            ldo, N, H, W, Cout, (int)iters, st, ph);
-    else if (m == 6)
-        hipLaunchKernelGGL(winograd_output6_kernel<false>, g, b, 0, s_, M, Tp * (size_t)Cm, Cm, bias, residual, ldr, rpi, out,
-                           ldo, N, H, W, Cout, (int)iters, st, ph);
-    else if (m == 2)
-        hipLaunchKernelGGL(winograd_output_kernel<2>, g, b, 0, s_, M, Tp * (size_t)Cm, Cm, splits, bias, residual, ldr, rpi, out,
-                           ldo, N, H, W, Cout, (int)iters, st, ph);
-    else
-        hipLaunchKernelGGL(winograd_output_kernel<4>, g, b, 0, s_, M, Tp * (size_t)Cm, Cm, splits, bias, residual, ldr, rpi, out,
-                           ldo, N, H, W, Cout, (int)iters, st, ph);
-    BBDM_CHECK_LAUNCH("winograd_output");
-    return BBDM_OK;
+        BBDM_CHECK_LAUNCH("winograd_output");
+        return BBDM_OK;
+    }, one_of<2, 4>(m));
 }
 
 extern "C" int bbdm_winograd_output_stats_f32(int m, const float* M, const float* bias, const float* residual, int ldr,
@@ -1689,14 +1570,12 @@ static int winograd_dy_planes(int m, const float* dy, int ld, void* dMt, float* 
     BBDM_REQUIRE(blocks < (1ll << 31), "winograd_dy_bf3p: too many workgroups");
     const dim3 g((unsigned)blocks);
     hipStream_t st = (hipStream_t)stream;
-#define BBDM_WINO_DYS(MO, NPL)                                                                                               \
-    hipLaunchKernelGGL((winograd_dy_split_kernel<MO, NPL>), g, dim3((MO + 2) * 64), 0, st, dy, ld, (unsigned char*)dMt, dm11, N, H, W, \
-                       Cout, nchunks, (long long)T, TG, plane_t, (int)(Tp / 16), dybound)
-    if (dybound) { if (m == 2) BBDM_WINO_DYS(2, 2); else if (m == 4) BBDM_WINO_DYS(4, 2); else if (m == 8) BBDM_WINO_DYS(8, 2); else BBDM_WINO_DYS(6, 2); }
-    else if (m == 2) BBDM_WINO_DYS(2, 3); else if (m == 4) BBDM_WINO_DYS(4, 3); else if (m == 8) BBDM_WINO_DYS(8, 3); else BBDM_WINO_DYS(6, 3);
-#undef BBDM_WINO_DYS
-    BBDM_CHECK_LAUNCH("winograd_dy_bf3p");
-    return BBDM_OK;
+    return dispatch([&](auto MO, auto NPL) {       // two planes (the fp16 pair) under dybound, three (bf16x3) without
+        hipLaunchKernelGGL((winograd_dy_split_kernel<MO(), NPL()>), g, dim3((MO() + 2) * 64), 0, st, dy, ld, (unsigned char*)dMt, dm11, N, H, W,
+                           Cout, nchunks, (long long)T, TG, plane_t, (int)(Tp / 16), dybound);
+        BBDM_CHECK_LAUNCH("winograd_dy_bf3p");
+        return BBDM_OK;
+    }, one_of<2, 4, 8, 6>(m), one_of<2, 3>(dybound ? 2 : 3));
 }
 
 // Test hook (exported, not part of the public header): the 1-D transforms above evaluated on the HOST, so that the CPU
@@ -1752,36 +1631,34 @@ extern "C" int bbdm_debug_winograd_transform_1d(int m, int which, const float* i
         }
         return BBDM_OK;
     }
-#define BBDM_WINO_1D(MO)                                                             \
-    do {                                                                             \
-        if (which == 0) {                                                            \
-            float d[MO + 2], t[MO + 2];                                              \
-            for (int i = 0; i < MO + 2; ++i) d[i] = in[i];                           \
-            bt_transform<MO>(d, t);                                                  \
-            for (int i = 0; i < MO + 2; ++i) out[i] = t[i];                          \
-        } else if (which == 1) {                                                     \
-            float v[MO + 2], r[MO];                                                  \
-            for (int i = 0; i < MO + 2; ++i) v[i] = in[i];                           \
-            at_transform<MO>(v, r);                                                  \
-            for (int i = 0; i < MO; ++i) out[i] = r[i];                              \
-        } else if (which == 2) {                                                     \
-            float g[3], u[MO + 2];                                                   \
-            for (int i = 0; i < 3; ++i) g[i] = in[i];                                \
-            g_transform<MO>(g, u);                                                   \
-            for (int i = 0; i < MO + 2; ++i) out[i] = u[i];                          \
-        } else if (which == 3) {                                                     \
-            float v[MO], r[MO + 2];                                                  \
-            for (int i = 0; i < MO; ++i) v[i] = in[i];                               \
-            a_transform<MO>(v, r);                                                   \
-            for (int i = 0; i < MO + 2; ++i) out[i] = r[i];                          \
-        } else {                                                                     \
-            float u[MO + 2], g[3];                                                   \
-            for (int i = 0; i < MO + 2; ++i) u[i] = in[i];                           \
-            gt_transform<MO>(u, g);                                                  \
-            for (int i = 0; i < 3; ++i) out[i] = g[i];                               \
-        }                                                                            \
-    } while (0)
-    if (m == 2) BBDM_WINO_1D(2); else if (m == 4) BBDM_WINO_1D(4); else BBDM_WINO_1D(6);
-#undef BBDM_WINO_1D
-    return BBDM_OK;
+    return dispatch([&](auto MO_) {
+        constexpr int MO = MO_(), AL = MO + 2;
+        if (which == 0) {
+            float d[AL], t[AL];
+            for (int i = 0; i < AL; ++i) d[i] = in[i];
+            bt_transform<MO>(d, t);
+            for (int i = 0; i < AL; ++i) out[i] = t[i];
+        } else if (which == 1) {
+            float v[AL], r[MO];
+            for (int i = 0; i < AL; ++i) v[i] = in[i];
+            at_transform<MO>(v, r);
+            for (int i = 0; i < MO; ++i) out[i] = r[i];
+        } else if (which == 2) {
+            float g[3], u[AL];
+            for (int i = 0; i < 3; ++i) g[i] = in[i];
+            g_transform<MO>(g, u);
+            for (int i = 0; i < AL; ++i) out[i] = u[i];
+        } else if (which == 3) {
+            float v[MO], r[AL];
+            for (int i = 0; i < MO; ++i) v[i] = in[i];
+            a_transform<MO>(v, r);
+            for (int i = 0; i < AL; ++i) out[i] = r[i];
+        } else {
+            float u[AL], g[3];
+            for (int i = 0; i < AL; ++i) u[i] = in[i];
+            gt_transform<MO>(u, g);
+            for (int i = 0; i < 3; ++i) out[i] = g[i];
+        }
+        return BBDM_OK;
+    }, one_of<2, 4, 6>(m));
 }

@@ -20,6 +20,7 @@
 // input transform, winograd_dy_split_kernel<8> (csrc/winograd.hip), bbdm_gemm_bf3p_tn_f32, and the finish kernels below with G^T . G in fp64
 // (3e-5); stages (1) - (3) of the fp32 form keep m <= 6.
 #include "winograd_math.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -430,15 +431,12 @@ int bbdm_gemm_tn_impl(const float* A, int lda, size_t a_stride, const float* B, 
     const long long blocks = (long long)cdiv(a.items, 8) * 8 * g.tilesM * g.tilesN;
     BBDM_REQUIRE(blocks < (1ll << 31), "gemm_tn: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (g.wm == 4) {
-        constexpr size_t lds = (size_t)2 * TKC * (256 + 32 + TBN + 32) * sizeof(float);
-        hipLaunchKernelGGL((gemm_tn_f32<4>), dim3((unsigned)blocks), dim3(512), lds, st, a);
-    } else {
-        constexpr size_t lds = (size_t)2 * TKC * (128 + 32 + TBN + 32) * sizeof(float);
-        hipLaunchKernelGGL((gemm_tn_f32<2>), dim3((unsigned)blocks), dim3(256), lds, st, a);
-    }
-    BBDM_CHECK_LAUNCH("gemm_tn");
-    return BBDM_OK;
+    return dispatch([&](auto WM) {
+        constexpr size_t lds = (size_t)2 * TKC * (WM() * 64 + 32 + TBN + 32) * sizeof(float);
+        hipLaunchKernelGGL((gemm_tn_f32<WM()>), dim3((unsigned)blocks), dim3(WM() * 128), lds, st, a);
+        BBDM_CHECK_LAUNCH("gemm_tn");
+        return BBDM_OK;
+    }, one_of<4, 2>(g.wm));
 }
 
 extern "C" int bbdm_winograd_dy_transform_f32(int m, const float* dy, int ld, float* dM, int N, int H, int W, int Cout,
@@ -455,11 +453,12 @@ extern "C" int bbdm_winograd_dy_transform_f32(int m, const float* dy, int ld, fl
     if (blocks > 16384) blocks = 16384;
     hipStream_t st = (hipStream_t)stream;
     const dim3 g((unsigned)blocks), b(256);
-    if (m == 2) hipLaunchKernelGGL((winograd_dy_kernel<2, float4>), g, b, 0, st, dy, ld, dM, N, H, W, Cout, plane);
-    else if (m == 4) hipLaunchKernelGGL((winograd_dy_kernel<4, float4>), g, b, 0, st, dy, ld, dM, N, H, W, Cout, plane);
-    else hipLaunchKernelGGL((winograd_dy_kernel<6, float2>), g, b, 0, st, dy, ld, dM, N, H, W, Cout, plane);
-    BBDM_CHECK_LAUNCH("winograd_dy");
-    return BBDM_OK;
+    return dispatch([&](auto MO) {
+        using V = std::conditional_t<MO() == 6, float2, float4>;
+        hipLaunchKernelGGL((winograd_dy_kernel<MO(), V>), g, b, 0, st, dy, ld, dM, N, H, W, Cout, plane);
+        BBDM_CHECK_LAUNCH("winograd_dy");
+        return BBDM_OK;
+    }, one_of<2, 4, 6>(m));
 }
 
 static int wgrad_finish_launch(int m, const float* dU, int splits, float* dw_oihw, int Cin, int Cout, const float* dm11, int T,
@@ -473,23 +472,21 @@ static int wgrad_finish_launch(int m, const float* dU, int splits, float* dw_oih
         const long long blocks = (long long)cdiv(Cout, 32) * cdiv(Cin, m == 8 ? 2 : 4) + bias_blocks;     // (FCI of wgrad_finish_nu_kernel)
         BBDM_REQUIRE(blocks < (1ll << 31), "winograd_wgrad_finish: grid too large");
         const dim3 g((unsigned)blocks);
-        if (m == 2) hipLaunchKernelGGL((wgrad_finish_nu_kernel<2>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout, dm11, T, dbias, bias_blocks);
-        else if (m == 4) hipLaunchKernelGGL((wgrad_finish_nu_kernel<4>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout, dm11, T, dbias, bias_blocks);
-        else if (m == 8) hipLaunchKernelGGL((wgrad_finish_nu_kernel<8>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout, dm11, T, dbias, bias_blocks);
-        else hipLaunchKernelGGL((wgrad_finish_nu_kernel<6>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout, dm11, T, dbias, bias_blocks);
-        BBDM_CHECK_LAUNCH("winograd_wgrad_finish");
-        return BBDM_OK;
+        return dispatch([&](auto MO) {
+            hipLaunchKernelGGL((wgrad_finish_nu_kernel<MO()>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout, dm11, T, dbias, bias_blocks);
+            BBDM_CHECK_LAUNCH("winograd_wgrad_finish");
+            return BBDM_OK;
+        }, one_of<2, 4, 8, 6>(m));
     }
     BBDM_REQUIRE(!dbias, "winograd_wgrad_finish_bias: Cout %% 4 == 0 and 16-byte aligned dU / dm11 required");
     const long long blocks = (long long)cdiv(Cout, 32) * cdiv(Cin, 8);
     BBDM_REQUIRE(blocks < (1ll << 31), "winograd_wgrad_finish: grid too large");
     const dim3 g((unsigned)blocks);
-    if (m == 2) hipLaunchKernelGGL((wgrad_finish_kernel<2>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout);
-    else if (m == 4) hipLaunchKernelGGL((wgrad_finish_kernel<4>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout);
-    else if (m == 8) hipLaunchKernelGGL((wgrad_finish_kernel<8>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout);
-    else hipLaunchKernelGGL((wgrad_finish_kernel<6>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout);
-    BBDM_CHECK_LAUNCH("winograd_wgrad_finish");
-    return BBDM_OK;
+    return dispatch([&](auto MO) {
+        hipLaunchKernelGGL((wgrad_finish_kernel<MO()>), g, b, 0, st, dU, splits, dw_oihw, Cin, Cout);
+        BBDM_CHECK_LAUNCH("winograd_wgrad_finish");
+        return BBDM_OK;
+    }, one_of<2, 4, 8, 6>(m));
 }
 
 extern "C" int bbdm_winograd_wgrad_finish_f32(int m, const float* dU, int splits, float* dw_oihw, int Cin, int Cout,
