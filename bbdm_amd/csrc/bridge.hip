@@ -5,6 +5,8 @@
 // directly), th.cat([x, context], 1) (openaimodel.py:742) and the NCHW<->NHWC hand-over at the UNet boundary.
 // Compiled with -ffp-contract=off: the reference evaluates these formulas as separate fp32 tensor ops.
 #include "common.h"
+#include "dispatch.h"
+#include "elementwise.h"
 #include "philox.h"
 #include "stats_acc.h"
 
@@ -14,6 +16,65 @@ __device__ __forceinline__ float predict_x0_one(int objective, float x_t, float 
     if (objective == 0) return x_t - pred;
     if (objective == 1) return (x_t - m * y - sig * pred) / (1.f - m);
     return y - pred;
+}
+
+// q_sample of one element (BBM.py:128-146): x_t and the target of the objective.
+struct QSample {
+    float x_t, target;
+};
+
+__device__ __forceinline__ QSample q_sample_one(int objective, float m, float sig, float a, float b, float e) {
+    QSample r;
+    if (objective == 0) r.target = m * (b - a) + sig * e;
+    else if (objective == 1) r.target = e;
+    else r.target = b - a;
+    r.x_t = (1.f - m) * a + m * b + sig * e;
+    return r;
+}
+
+// The coefficients of one bridge step t -> t_next (BBM.py:186-201); a last step uses m_t and sig_obj alone and ignores t_next and eta.
+struct StepCoef {
+    float m_t, sig_obj, m_nt, sigma_t, coef;
+};
+
+__device__ __forceinline__ StepCoef step_coef(const float* __restrict__ m_tab, const float* __restrict__ var_tab, int64_t t,
+                                              int64_t t_next, int is_last, float eta) {
+    StepCoef c;
+    c.m_t = m_tab[t];
+    const float var_t = var_tab[t];
+    c.sig_obj = sqrtf(var_t);
+    c.m_nt = 0.f, c.sigma_t = 0.f, c.coef = 0.f;
+    if (!is_last) {
+        c.m_nt = m_tab[t_next];
+        const float var_nt = var_tab[t_next];
+        // sigma2_t = (var_t - var_nt * (1 - m_t)**2 / (1 - m_nt)**2) * var_nt / var_t       (BBM.py:194)
+        const float a = (1.f - c.m_t) * (1.f - c.m_t);
+        const float b = (1.f - c.m_nt) * (1.f - c.m_nt);
+        const float sigma2 = (var_t - var_nt * a / b) * var_nt / var_t;
+        c.sigma_t = sqrtf(sigma2) * eta;
+        c.coef = sqrtf((var_nt - sigma2) / var_t);
+    }
+    return c;
+}
+
+// The step of one element: x0 by objective, clip, then the last step's x_next = x0_recon or the mean + sigma_t * noise.
+struct StepOut {
+    float x0_recon, x_next;
+};
+
+__device__ __forceinline__ StepOut step_one(const StepCoef& c, int objective, int clip, int is_last, float xt, float yy, float pred,
+                                            float noise) {
+    StepOut r;
+    r.x0_recon = predict_x0_one(objective, xt, yy, pred, c.m_t, c.sig_obj);
+    if (clip) r.x0_recon = fminf(fmaxf(r.x0_recon, -1.f), 1.f);
+    if (is_last) {
+        r.x_next = r.x0_recon;
+    } else {
+        // (1 - m_nt) x0 + m_nt y + sqrt((var_nt - sigma2)/var_t) (x_t - (1 - m_t) x0 - m_t y) + sigma_t eps
+        const float mean = (1.f - c.m_nt) * r.x0_recon + c.m_nt * yy + c.coef * (xt - (1.f - c.m_t) * r.x0_recon - c.m_t * yy);
+        r.x_next = mean + c.sigma_t * noise;
+    }
+    return r;
 }
 
 __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ y,
@@ -26,13 +87,9 @@ __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __res
         const int64_t tt = t[n];
         const float m = m_t[tt];
         const float sig = sqrtf(var_t[tt]);
-        const float a = x0[i], b = y[i], e = noise[i];
-        float tg;
-        if (objective == 0) tg = m * (b - a) + sig * e;
-        else if (objective == 1) tg = e;
-        else tg = b - a;
-        x_t[i] = (1.f - m) * a + m * b + sig * e;
-        target[i] = tg;
+        const QSample r = q_sample_one(objective, m, sig, x0[i], y[i], noise[i]);
+        x_t[i] = r.x_t;
+        target[i] = r.target;
     }
 }
 
@@ -52,41 +109,19 @@ __global__ void p_step_kernel(const float* __restrict__ x_t, const float* __rest
                               const float* __restrict__ var_tab, int t, int t_next, int is_last, float eta, int clip,
                               int objective, float* __restrict__ x_next, float* __restrict__ x0_recon,
                               float* __restrict__ x_next_alias, size_t total) {
-    const float m_t = m_tab[t], var_t = var_tab[t];
-    const float sig_obj = sqrtf(var_t);
-    float m_nt = 0.f, sigma_t = 0.f, coef = 0.f;
-    if (!is_last) {
-        m_nt = m_tab[t_next];
-        const float var_nt = var_tab[t_next];
-        // sigma2_t = (var_t - var_nt * (1 - m_t)**2 / (1 - m_nt)**2) * var_nt / var_t       (BBM.py:194)
-        const float a = (1.f - m_t) * (1.f - m_t);
-        const float b = (1.f - m_nt) * (1.f - m_nt);
-        const float sigma2 = (var_t - var_nt * a / b) * var_nt / var_t;
-        sigma_t = sqrtf(sigma2) * eta;
-        coef = sqrtf((var_nt - sigma2) / var_t);
-    }
+    const StepCoef c = step_coef(m_tab, var_tab, t, t_next, is_last, eta);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const float xt = x_t[i], yy = y[i];
-        float x0r = predict_x0_one(objective, xt, yy, pred[i], m_t, sig_obj);
-        if (clip) x0r = fminf(fmaxf(x0r, -1.f), 1.f);
-        x0_recon[i] = x0r;
-        if (is_last) {
-            x_next[i] = x0r;
-            if (x_next_alias) x_next_alias[i] = x0r;
-        } else {
-            // (1 - m_nt) x0 + m_nt y + sqrt((var_nt - sigma2)/var_t) (x_t - (1 - m_t) x0 - m_t y) + sigma_t eps
-            const float mean = (1.f - m_nt) * x0r + m_nt * yy + coef * (xt - (1.f - m_t) * x0r - m_t * yy);
-            const float xn = mean + sigma_t * noise[i];
-            x_next[i] = xn;
-            if (x_next_alias) x_next_alias[i] = xn;        // second copy: the caller's input buffer of the NEXT step (see the header)
-        }
+        const StepOut r = step_one(c, objective, clip, is_last, x_t[i], y[i], pred[i], is_last ? 0.f : noise[i]);   // no noise read by a last step
+        x0_recon[i] = r.x0_recon;
+        x_next[i] = r.x_next;
+        if (x_next_alias) x_next_alias[i] = r.x_next;      // second copy: the caller's input buffer of the NEXT step (see the header)
     }
 }
 
 // Where a per-image launch takes eta and the clip decision of image n from -- the P of the two kernels below.
 // UniformParams: one launch argument each, and the flag word is the state (the kernel arguments of the *_batched_ / *_philox_ entry
-// points, unchanged).  RequestParams (the *_requests_* entry points): eta[n] from a device array, read only by an image that takes a
-// step with noise; bits 0-1 of the flag word are the state and bit 2 says "clip this image".
+// points, unchanged).  RequestParams (the *_requests_* entry points): eta[n] from a device array (every active image reads its
+// entry and its next step; a last step ignores both); bits 0-1 of the flag word are the state and bit 2 says "clip this image".
 struct UniformParams {
     float eta_;
     int clip_;
@@ -120,65 +155,22 @@ __global__ void p_step_batched_kernel(const float* __restrict__ x_t, const float
     if (state == 2) return;
     const int is_last = state == 1;
     const int clip = params.clip(flag);
-    const int64_t t = t_arr[n];
-    const float m_t = m_tab[t], var_t = var_tab[t];
-    const float sig_obj = sqrtf(var_t);
-    float m_nt = 0.f, sigma_t = 0.f, coef = 0.f;
-    if (!is_last) {
-        const int64_t t_next = t_next_arr[n];
-        m_nt = m_tab[t_next];
-        const float var_nt = var_tab[t_next];
-        const float a = (1.f - m_t) * (1.f - m_t);
-        const float b = (1.f - m_nt) * (1.f - m_nt);
-        const float sigma2 = (var_t - var_nt * a / b) * var_nt / var_t;
-        sigma_t = sqrtf(sigma2) * params.eta(n);
-        coef = sqrtf((var_nt - sigma2) / var_t);
-    }
+    const StepCoef c = step_coef(m_tab, var_tab, t_arr[n], t_next_arr[n], is_last, params.eta(n));
     const size_t base = (size_t)n * per_sample;
     for (size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x; k < (size_t)per_sample; k += (size_t)gridDim.x * blockDim.x) {
         const size_t i = base + k;
-        const float xt = x_t[i], yy = y[i];
-        float x0r = predict_x0_one(objective, xt, yy, pred[i], m_t, sig_obj);
-        if (clip) x0r = fminf(fmaxf(x0r, -1.f), 1.f);
-        x0_recon[i] = x0r;
-        if (is_last) {
-            x_next[i] = x0r;
-            if (x_next_alias) x_next_alias[i] = x0r;
-        } else {
-            const float mean = (1.f - m_nt) * x0r + m_nt * yy + coef * (xt - (1.f - m_t) * x0r - m_t * yy);
-            const float xn = mean + sigma_t * noise[i];
-            x_next[i] = xn;
-            if (x_next_alias) x_next_alias[i] = xn;
-        }
+        const StepOut r = step_one(c, objective, clip, is_last, x_t[i], y[i], pred[i], is_last ? 0.f : noise[i]);
+        x0_recon[i] = r.x0_recon;
+        x_next[i] = r.x_next;
+        if (x_next_alias) x_next_alias[i] = r.x_next;
     }
 }
 
 // ---- seed-addressed noise (philox.h): the normals are a function of (seed, ordinal, domain, element) and never touch memory in the
 // fused kernels.  One image per blockIdx.y; a thread owns groups of four consecutive elements of it (one Philox call per group:
 // its four words are the group's four normals).  VEC: per_sample % 4 == 0 and 16-byte aligned pointers (the launchers check), one
-// 128-bit access per tensor and group; otherwise element accesses with the image's tail (per_sample % 4 elements) guarded.
-template <bool VEC>
-__device__ __forceinline__ void load_group(const float* __restrict__ p, int count, float v[4]) {
-    if (VEC) {
-        const float4 f = *reinterpret_cast<const float4*>(p);
-        v[0] = f.x, v[1] = f.y, v[2] = f.z, v[3] = f.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = j < count ? p[j] : 0.f;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store_group(float* __restrict__ p, int count, const float v[4]) {
-    if (VEC) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < count) p[j] = v[j];
-    }
-}
-
+// 128-bit access per tensor and group; otherwise element accesses with the image's tail (per_sample % 4 elements) guarded
+// (load_group / store_group of elementwise.h).
 template <bool VEC>
 __global__ void __launch_bounds__(256) philox_normal_kernel(float* __restrict__ out, const int64_t* __restrict__ seed_arr,
                                                             const int64_t* __restrict__ ordinal_arr, unsigned domain,
@@ -224,23 +216,8 @@ __global__ void __launch_bounds__(256) p_step_philox_kernel(const float* __restr
     if (state == 2) return;
     const int is_last = state == 1;
     const int clip = params.clip(flag);
-    const int64_t t = t_arr[n];
-    const float m_t = m_tab[t], var_t = var_tab[t];
-    const float sig_obj = sqrtf(var_t);
-    float m_nt = 0.f, sigma_t = 0.f, coef = 0.f;
-    int64_t seed = 0, ordinal = 0;
-    if (!is_last) {
-        const int64_t t_next = t_next_arr[n];
-        m_nt = m_tab[t_next];
-        const float var_nt = var_tab[t_next];
-        const float a = (1.f - m_t) * (1.f - m_t);
-        const float b = (1.f - m_nt) * (1.f - m_nt);
-        const float sigma2 = (var_t - var_nt * a / b) * var_nt / var_t;
-        sigma_t = sqrtf(sigma2) * params.eta(n);
-        coef = sqrtf((var_nt - sigma2) / var_t);
-        seed = seed_arr[n];
-        ordinal = ordinal_arr[n];
-    }
+    const int64_t seed = seed_arr[n], ordinal = ordinal_arr[n];      // (a last step reads them too, and generates nothing)
+    const StepCoef c = step_coef(m_tab, var_tab, t_arr[n], t_next_arr[n], is_last, params.eta(n));
     const size_t base = (size_t)n * per_sample;
     const unsigned groups = ((unsigned)per_sample + 3u) / 4u;
     for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < groups; q += gridDim.x * 256u) {
@@ -253,15 +230,9 @@ __global__ void __launch_bounds__(256) p_step_philox_kernel(const float* __restr
         if (!is_last) philox_normal4(seed, ordinal, BBDM_NOISE_P_SAMPLE, q, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float x0r = predict_x0_one(objective, xt[j], yy[j], pr[j], m_t, sig_obj);
-            if (clip) x0r = fminf(fmaxf(x0r, -1.f), 1.f);
-            x0v[j] = x0r;
-            if (is_last) {
-                xnv[j] = x0r;
-            } else {
-                const float mean = (1.f - m_nt) * x0r + m_nt * yy[j] + coef * (xt[j] - (1.f - m_t) * x0r - m_t * yy[j]);
-                xnv[j] = mean + sigma_t * z[j];
-            }
+            const StepOut r = step_one(c, objective, clip, is_last, xt[j], yy[j], pr[j], z[j]);
+            x0v[j] = r.x0_recon;
+            xnv[j] = r.x_next;
         }
         store_group<VEC>(x0_recon + i, count, x0v);
         store_group<VEC>(x_next + i, count, xnv);
@@ -293,13 +264,9 @@ __global__ void __launch_bounds__(256) q_sample_philox_kernel(const float* __res
         philox_normal4(seed, ordinal, BBDM_NOISE_Q_SAMPLE, q, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float a = av[j], b = bv[j], e = z[j];
-            float tg;
-            if (objective == 0) tg = m * (b - a) + sig * e;
-            else if (objective == 1) tg = e;
-            else tg = b - a;
-            xv[j] = (1.f - m) * a + m * b + sig * e;
-            tv[j] = tg;
+            const QSample r = q_sample_one(objective, m, sig, av[j], bv[j], z[j]);
+            xv[j] = r.x_t;
+            tv[j] = r.target;
         }
         store_group<VEC>(x_t + i, count, xv);
         store_group<VEC>(target + i, count, tv);
@@ -366,13 +333,9 @@ __global__ void __launch_bounds__(256) q_sample_cached_kernel(const float* __res
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float a = av[j], b = bv[j], e = z[j];
-            float tg;
-            if (objective == 0) tg = m * (b - a) + sig * e;
-            else if (objective == 1) tg = e;
-            else tg = b - a;
-            xv[j] = (1.f - m) * a + m * b + sig * e;
-            tv[j] = tg;
+            const QSample r = q_sample_one(objective, m, sig, av[j], bv[j], z[j]);
+            xv[j] = r.x_t;
+            tv[j] = r.target;
         }
         store_group<VEC>(x_t + base + k, count, xv);
         store_group<VEC>(target + base + k, count, tv);
@@ -390,7 +353,6 @@ __global__ void __launch_bounds__(256) q_sample_cached_kernel(const float* __res
 template <bool VEC, bool SQ>
 __global__ void __launch_bounds__(256) latent_stats_kernel(const float* __restrict__ z, int64_t M, int C, int hw,
                                                            unsigned long long* __restrict__ cells, double count) {
-    __shared__ double red[4];
     const int c = blockIdx.y;
     double mean = 0.0;
     if (SQ) mean = (double)(float)(sa_load(cells + (size_t)c * SA_W) / count);
@@ -410,12 +372,9 @@ __global__ void __launch_bounds__(256) latent_stats_kernel(const float* __restri
                     s += SQ ? d * d : d;
                 }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) sa_add(cell, (red[0] + red[1]) + (red[2] + red[3]));
-        __syncthreads();                                   // red is rewritten by the next row
+        const double total = block_sum_down(s);
+        if (threadIdx.x == 0) sa_add(cell, total);
+        __syncthreads();                                   // block_sum_down's partials are rewritten by the next row
     }
 }
 
@@ -431,17 +390,10 @@ __global__ void latent_stats_final_kernel(const unsigned long long* __restrict__
 
 __global__ void __launch_bounds__(256) loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            unsigned long long* __restrict__ partial, size_t count, int loss_type) {
-    __shared__ double red[4];
     double s = 0.0;
-    for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
-        const float d = a[i] - b[i];
-        s += loss_type == 0 ? (double)fabsf(d) : (double)d * (double)d;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) sa_add(partial, (red[0] + red[1]) + (red[2] + red[3]));      // exact limb cell: any block order, same bits
+    for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) s += loss_term(a[i], b[i], loss_type);
+    const double total = block_sum_down(s);
+    if (threadIdx.x == 0) sa_add(partial, total);          // exact limb cell: any block order, same bits
 }
 
 __global__ void loss_final_kernel(const unsigned long long* __restrict__ partial, float* __restrict__ out, double inv_count) {
@@ -485,18 +437,13 @@ __global__ void nhwc_to_nchw_kernel(const float* __restrict__ x, int ldx, float*
     }
 }
 
-inline unsigned ew_blocks(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (unsigned)(b > 8192 ? 8192 : (b ? b : 1));
+// The argument checks of a one-image-per-blockIdx.y launch (N is gridDim.y).  counter: the kernel numbers its groups of four in the
+// 32-bit counter word of Philox.
+int check_per_image(const char* what, int N, int per_sample, int objective, bool counter) {
+    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "%s: bad args", what);
+    BBDM_REQUIRE(!counter || (unsigned long long)per_sample / 4 < (1ull << 32), "%s: per_sample / 4 must fit the 32-bit counter word", what);
+    return BBDM_OK;
 }
-
-// grid of the one-image-per-blockIdx.y kernels above: groups of four elements, 256 per block
-inline dim3 group_grid(int N, int per_sample) {
-    const size_t b = ((size_t)per_sample + 1023) / 1024;
-    return dim3((unsigned)(b > 2048 ? 2048 : b), (unsigned)N);
-}
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // The checks and the launch shared by the uniform and the per-request entry point of each per-image kernel (P as above).
 template <class P>
@@ -506,7 +453,7 @@ int launch_p_step_batched(const char* what, const float* x_t, const float* y, co
                           int N, int per_sample, void* stream) {
     BBDM_REQUIRE(x_t && y && pred && noise && m_t && variance_t && t && t_next && flag && x_next && x0_recon,
                  "%s: null pointer", what);
-    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "%s: bad args", what);
+    if (const int rc = check_per_image(what, N, per_sample, objective, false)) return rc;
     const size_t b = ((size_t)per_sample + 255) / 256;
     const unsigned bx = (unsigned)(b > 2048 ? 2048 : b);
     hipLaunchKernelGGL(p_step_batched_kernel<P>, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x_t, y, pred, noise,
@@ -522,19 +469,15 @@ int launch_p_step_philox(const char* what, const float* x_t, const float* y, con
                          float* x_next_alias, int N, int per_sample, void* stream) {
     BBDM_REQUIRE(x_t && y && pred && seed && ordinal && m_t && variance_t && t && t_next && flag && x_next && x0_recon,
                  "%s: null pointer", what);
-    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "%s: bad args", what);
-    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32), "%s: per_sample / 4 must fit the 32-bit counter word", what);
-    const dim3 grid = group_grid(N, per_sample);
+    if (const int rc = check_per_image(what, N, per_sample, objective, true)) return rc;
     const bool vec = per_sample % 4 == 0 && aligned16(x_t) && aligned16(y) && aligned16(pred) && aligned16(x_next) &&
                      aligned16(x0_recon) && aligned16(x_next_alias);
-    if (vec)
-        hipLaunchKernelGGL((p_step_philox_kernel<true, P>), grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal,
-                           m_t, variance_t, t, t_next, flag, params, objective, x_next, x0_recon, x_next_alias, per_sample);
-    else
-        hipLaunchKernelGGL((p_step_philox_kernel<false, P>), grid, dim3(256), 0, (hipStream_t)stream, x_t, y, pred, seed, ordinal,
-                           m_t, variance_t, t, t_next, flag, params, objective, x_next, x0_recon, x_next_alias, per_sample);
-    BBDM_CHECK_LAUNCH(what);
-    return BBDM_OK;
+    return dispatch([&](auto VEC) {
+        hipLaunchKernelGGL((p_step_philox_kernel<VEC(), P>), group_grid(N, per_sample), dim3(256), 0, (hipStream_t)stream, x_t, y, pred,
+                           seed, ordinal, m_t, variance_t, t, t_next, flag, params, objective, x_next, x0_recon, x_next_alias, per_sample);
+        BBDM_CHECK_LAUNCH(what);
+        return BBDM_OK;
+    }, vec);
 }
 
 // The checks and the launch shared by the two cached q_sample entry points (PHILOX as in the kernel).
@@ -548,23 +491,19 @@ int launch_q_sample_cached(const char* what, const float* ori, const float* cond
     BBDM_REQUIRE(PHILOX ? (seed && ordinal) : noise != nullptr, "%s: null noise source", what);
     const int stats = (ori_mean != nullptr) + (ori_std != nullptr) + (cond_mean != nullptr) + (cond_std != nullptr);
     BBDM_REQUIRE(stats == 0 || stats == 4, "%s: pass all four of ori_mean / ori_std / cond_mean / cond_std or none", what);
-    BBDM_REQUIRE(M > 0 && N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "%s: bad args", what);
+    BBDM_REQUIRE(M > 0, "%s: bad args", what);
+    if (const int rc = check_per_image(what, N, per_sample, objective, true)) return rc;
     BBDM_REQUIRE(hw > 0 && per_sample % hw == 0, "%s: per_sample must be a multiple of hw", what);
-    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32), "%s: per_sample / 4 must fit the 32-bit counter word", what);
-    const dim3 grid = group_grid(N, per_sample);
     // (per_sample % 4 == 0 makes every gathered row as aligned as its tensor)
     const bool vec = per_sample % 4 == 0 && aligned16(ori) && aligned16(cond) && aligned16(noise) && aligned16(x_t) &&
                      aligned16(target) && aligned16(y_out);
-    if (vec)
-        hipLaunchKernelGGL((q_sample_cached_kernel<true, PHILOX>), grid, dim3(256), 0, (hipStream_t)stream, ori, cond, (int64_t)M,
-                           idx_ori, idx_cond, ori_mean, ori_std, cond_mean, cond_std, hw, noise, seed, ordinal, t, m_t, variance_t,
-                           x_t, target, y_out, per_sample, objective);
-    else
-        hipLaunchKernelGGL((q_sample_cached_kernel<false, PHILOX>), grid, dim3(256), 0, (hipStream_t)stream, ori, cond, (int64_t)M,
-                           idx_ori, idx_cond, ori_mean, ori_std, cond_mean, cond_std, hw, noise, seed, ordinal, t, m_t, variance_t,
-                           x_t, target, y_out, per_sample, objective);
-    BBDM_CHECK_LAUNCH(what);
-    return BBDM_OK;
+    return dispatch([&](auto VEC) {
+        hipLaunchKernelGGL((q_sample_cached_kernel<VEC(), PHILOX>), group_grid(N, per_sample), dim3(256), 0, (hipStream_t)stream, ori, cond,
+                           (int64_t)M, idx_ori, idx_cond, ori_mean, ori_std, cond_mean, cond_std, hw, noise, seed, ordinal, t, m_t,
+                           variance_t, x_t, target, y_out, per_sample, objective);
+        BBDM_CHECK_LAUNCH(what);
+        return BBDM_OK;
+    }, vec);
 }
 
 }  // namespace
@@ -630,17 +569,14 @@ extern "C" int bbdm_bb_p_sample_step_requests_f32(const float* x_t, const float*
 extern "C" int bbdm_philox_normal_f32(float* out, const int64_t* seed, const int64_t* ordinal, int domain, int N,
                                       int per_sample, void* stream) {
     BBDM_REQUIRE(out && seed && ordinal, "philox_normal: null pointer");
-    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && domain >= 0, "philox_normal: bad args");
-    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32), "philox_normal: per_sample / 4 must fit the 32-bit counter word");
-    const dim3 grid = group_grid(N, per_sample);
-    if (per_sample % 4 == 0 && aligned16(out))
-        hipLaunchKernelGGL(philox_normal_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, out, seed, ordinal,
+    BBDM_REQUIRE(domain >= 0, "philox_normal: bad args");
+    if (const int rc = check_per_image("philox_normal", N, per_sample, 0, true)) return rc;
+    return dispatch([&](auto VEC) {
+        hipLaunchKernelGGL(philox_normal_kernel<VEC()>, group_grid(N, per_sample), dim3(256), 0, (hipStream_t)stream, out, seed, ordinal,
                            (unsigned)domain, per_sample);
-    else
-        hipLaunchKernelGGL(philox_normal_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, seed, ordinal,
-                           (unsigned)domain, per_sample);
-    BBDM_CHECK_LAUNCH("philox_normal");
-    return BBDM_OK;
+        BBDM_CHECK_LAUNCH("philox_normal");
+        return BBDM_OK;
+    }, per_sample % 4 == 0 && aligned16(out));
 }
 
 extern "C" int bbdm_philox_raw_u32(const uint32_t* counter_key, uint32_t* out, int n, void* stream) {
@@ -674,18 +610,13 @@ extern "C" int bbdm_bb_q_sample_philox_f32(const float* x0, const float* y, cons
                                            const int64_t* t, const float* m_t, const float* variance_t, float* x_t,
                                            float* target, int N, int per_sample, int objective, void* stream) {
     BBDM_REQUIRE(x0 && y && seed && ordinal && t && m_t && variance_t && x_t && target, "q_sample_philox: null pointer");
-    BBDM_REQUIRE(N > 0 && N <= 65535 && per_sample > 0 && objective >= 0 && objective <= 2, "q_sample_philox: bad args");
-    BBDM_REQUIRE((unsigned long long)per_sample / 4 < (1ull << 32),
-                 "q_sample_philox: per_sample / 4 must fit the 32-bit counter word");
-    const dim3 grid = group_grid(N, per_sample);
-    if (per_sample % 4 == 0 && aligned16(x0) && aligned16(y) && aligned16(x_t) && aligned16(target))
-        hipLaunchKernelGGL(q_sample_philox_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x0, y, seed, ordinal, t, m_t,
-                           variance_t, x_t, target, per_sample, objective);
-    else
-        hipLaunchKernelGGL(q_sample_philox_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x0, y, seed, ordinal, t, m_t,
-                           variance_t, x_t, target, per_sample, objective);
-    BBDM_CHECK_LAUNCH("q_sample_philox");
-    return BBDM_OK;
+    if (const int rc = check_per_image("q_sample_philox", N, per_sample, objective, true)) return rc;
+    return dispatch([&](auto VEC) {
+        hipLaunchKernelGGL(q_sample_philox_kernel<VEC()>, group_grid(N, per_sample), dim3(256), 0, (hipStream_t)stream, x0, y, seed,
+                           ordinal, t, m_t, variance_t, x_t, target, per_sample, objective);
+        BBDM_CHECK_LAUNCH("q_sample_philox");
+        return BBDM_OK;
+    }, per_sample % 4 == 0 && aligned16(x0) && aligned16(y) && aligned16(x_t) && aligned16(target));
 }
 
 extern "C" int bbdm_bb_q_sample_cached_f32(const float* ori, const float* cond, long long M, const int64_t* idx_ori,
@@ -718,13 +649,14 @@ extern "C" int bbdm_latent_channel_stats_f32(const float* z, long long M, int C,
     const long long want = row_blocks ? row_blocks : 1024;
     const dim3 grid((unsigned)(want < M ? want : M), (unsigned)C);
     const double count = (double)M * (double)hw;
-    if (hw % 4 == 0 && aligned16(z)) {
-        hipLaunchKernelGGL((latent_stats_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
-        hipLaunchKernelGGL((latent_stats_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
-    } else {
-        hipLaunchKernelGGL((latent_stats_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
-        hipLaunchKernelGGL((latent_stats_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
-    }
+    const bool vec = hw % 4 == 0 && aligned16(z);
+    const auto pass = [&](auto VEC, auto SQ) {              // SQ: the squared deviations from the mean the first pass gives
+        hipLaunchKernelGGL((latent_stats_kernel<VEC(), SQ()>), grid, dim3(256), 0, (hipStream_t)stream, z, (int64_t)M, C, hw, cell, count);
+        BBDM_CHECK_LAUNCH("latent_channel_stats");
+        return BBDM_OK;
+    };
+    if (const int rc = dispatch(pass, vec, false)) return rc;
+    if (const int rc = dispatch(pass, vec, true)) return rc;
     hipLaunchKernelGGL(latent_stats_final_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cell, C, count,
                        mean, var, stdev);
     BBDM_CHECK_LAUNCH("latent_channel_stats");

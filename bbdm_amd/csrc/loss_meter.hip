@@ -13,6 +13,8 @@
 // on N, on the image's place in the batch, or on which of the two load paths runs.  The table therefore has the same bits for any
 // batch size, arrival order or split over ranks.  Built with -ffp-contract=off like bridge.hip.
 #include "common.h"
+#include "dispatch.h"
+#include "elementwise.h"
 #include "stats_acc.h"
 
 namespace {
@@ -21,19 +23,13 @@ typedef unsigned long long u64;
 
 constexpr int LM_CHUNK = 2048;           // elements of one image per workgroup: two groups of four per thread
 
-__device__ __forceinline__ double lm_term(float x, float y, int loss_type) {
-    const float d = x - y;               // the difference in fp32, the sum in fp64: loss_partial_kernel's arithmetic (bridge.hip)
-    return loss_type == 0 ? (double)fabsf(d) : (double)d * (double)d;
-}
-
 // grid (cdiv(per_sample, LM_CHUNK) * N): block = (image, chunk).  Thread `tid` owns the groups of four elements tid and tid + 256 of
 // its chunk and adds their terms in element order -- VEC: one 16-byte load per group and tensor (per_sample % 4 == 0 and 16-byte
 // aligned pointers, the launcher checks), else element loads of the SAME groups with the tail cut at per_sample: the same sequence of
-// additions, so the same partial.
+// additions, so the same partial.  The term is loss_partial_kernel's (bridge.hip): loss_term of elementwise.h.
 template <bool VEC>
 __global__ void __launch_bounds__(256) lm_per_image_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            u64* __restrict__ cells, int per_sample, int chunks, int loss_type) {
-    __shared__ double red[4];
     const int n = blockIdx.x / chunks, chunk = blockIdx.x - n * chunks;
     const float* pa = a + (size_t)n * per_sample;
     const float* pb = b + (size_t)n * per_sample;
@@ -45,20 +41,17 @@ __global__ void __launch_bounds__(256) lm_per_image_kernel(const float* __restri
         if (VEC) {
             const float4 x = *reinterpret_cast<const float4*>(pa + e0);
             const float4 y = *reinterpret_cast<const float4*>(pb + e0);
-            s += lm_term(x.x, y.x, loss_type);
-            s += lm_term(x.y, y.y, loss_type);
-            s += lm_term(x.z, y.z, loss_type);
-            s += lm_term(x.w, y.w, loss_type);
+            s += loss_term(x.x, y.x, loss_type);
+            s += loss_term(x.y, y.y, loss_type);
+            s += loss_term(x.z, y.z, loss_type);
+            s += loss_term(x.w, y.w, loss_type);
         } else {
             const int e1 = e0 + 4 < per_sample ? e0 + 4 : per_sample;
-            for (int e = e0; e < e1; ++e) s += lm_term(pa[e], pb[e], loss_type);
+            for (int e = e0; e < e1; ++e) s += loss_term(pa[e], pb[e], loss_type);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) sa_add(cells + (size_t)n * SA_W, (red[0] + red[1]) + (red[2] + red[3]));
+    const double total = block_sum_down(s);
+    if (threadIdx.x == 0) sa_add(cells + (size_t)n * SA_W, total);
 }
 
 __global__ void lm_per_image_final_kernel(const u64* __restrict__ cells, float* __restrict__ per_image, int N, double per_sample) {
@@ -91,8 +84,6 @@ __global__ void lm_read_kernel(const u64* __restrict__ meter, double* __restrict
     else sum[i >> 1] = v;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int bbdm_loss_meter_per_image_f32(const float* a, const float* b, unsigned long long* cells, float* per_image, int N,
@@ -102,10 +93,10 @@ extern "C" int bbdm_loss_meter_per_image_f32(const float* a, const float* b, uns
     const int chunks = cdiv(per_sample, LM_CHUNK);
     BBDM_REQUIRE((long long)chunks * N < (1ll << 31), "loss_meter_per_image: N=%d x %d blocks per image exceed the grid", N, chunks);
     const dim3 grid((unsigned)(chunks * N));
-    if (per_sample % 4 == 0 && aligned16(a) && aligned16(b))
-        hipLaunchKernelGGL(lm_per_image_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, b, cells, per_sample, chunks, loss_type);
-    else
-        hipLaunchKernelGGL(lm_per_image_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, b, cells, per_sample, chunks, loss_type);
+    dispatch([&](auto VEC) {
+        hipLaunchKernelGGL(lm_per_image_kernel<VEC()>, grid, dim3(256), 0, (hipStream_t)stream, a, b, cells, per_sample, chunks, loss_type);
+        return BBDM_OK;
+    }, per_sample % 4 == 0 && aligned16(a) && aligned16(b));
     if (per_image)
         hipLaunchKernelGGL(lm_per_image_final_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, cells, per_image, N,
                            (double)per_sample);

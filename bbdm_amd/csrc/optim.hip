@@ -35,128 +35,55 @@
 //                        where torch's would be Inf (an Inf gradient) or a finite number > 65 536.
 //   grad_finalize_kernel one workgroup: norm, coef = min(1, (1 / (norm + 1e-6)) * max_norm) in fp32 as torch forms it (NaN stays NaN), ok, and
 //                        the device counter of skipped steps.
-//   adam_ema_kernel<true> g * coef (one rounding, as grads.mul_(coef)) in front of adam_one; ok == 0 under skip_nonfinite: no Adam update
-//                        (the EMA part still runs, as the runner's ema.update would).
+//   rule_ema_kernel<.., CLIP = true>  g * coef (one rounding, as grads.mul_(coef)) in front of the rule; ok == 0 under skip_nonfinite: no
+//                        update (the EMA part still runs, as the runner's ema.update would).
 //   grad_scale_kernel    g *= coef (the standalone clip_grad_norm_).
-//   rule_ema_kernel      the SGD and RMSprop rules (runners/utils.py:52-55) with the same mapping, clip buffer and EMA part: below.
+// rule_ema_kernel is the one update kernel: Adam, and the SGD and RMSprop rules (runners/utils.py:52-55), as instances of one template
+// on one walk over the chunk (chunk_walk), with the same clip buffer and EMA part.
 #include "common.h"
+#include "dispatch.h"
 #include "stats_acc.h"
 
 namespace {
 
 constexpr int CHUNK = 16384;       // elements per table entry = per workgroup (64 per thread)
 
+enum { RULE_SGD = 0, RULE_RMSPROP = 1, RULE_ADAM = 2 };
+
+// One launch's arguments, whatever the rule (a rule reads its own fields; the launchers zero the rest).
 struct OptArgs {
     const BbdmOptChunk* table;
-    float lr_over_bc1, sqrt_bc2, b1c, b2, b2c, eps, wd;     // b1c = 1 - beta1, b2c = 1 - beta2
+    float lr, wd, eps;                                            // Adam: lr = lr / bc1
+    float sqrt_bc2, b1c, b2, b2c;                                 // Adam: b1c = 1 - beta1, b2c = 1 - beta2
+    float mom, damp_c, alpha, alpha_c;                            // SGD / RMSprop: damp_c = 1 - dampening, alpha_c = 1 - alpha
+    int nesterov, first;                                          // first: SGD's first step with momentum: buf = g' (buf is not read)
     float ema_decay, ema_c;                                       // ema_c = 1 - decay
-    int do_adam, ema_mode;                                        // ema_mode: 0 none, 1 decay, 2 copy
-    const float* clip;                                            // adam_ema_kernel<true>: {norm, coef, ok, 0} of grad_finalize_kernel
+    int ema_mode;                                                 // 0 none, 1 decay, 2 copy
+    const float* clip;                                            // CLIP kernels: {norm, coef, ok, 0} of grad_finalize_kernel
     int skip_nonfinite;
 };
 
-__device__ __forceinline__ void adam_one(const OptArgs& a, float& p, float g, float& m, float& v) {
-    if (a.wd != 0.f) g = fmaf(a.wd, p, g);          // grad.add(param, alpha=wd): one rounding in ATen's kernels
-    // at::lerp: |w| < 0.5 ? a + w (b - a) : b - (b - a) (1 - w),  w = 1 - beta1
-    m = a.b1c < 0.5f ? m + a.b1c * (g - m) : g - (g - m) * (1.f - a.b1c);
-    v = v * a.b2 + a.b2c * g * g;
-    const float denom = sqrtf(v) / a.sqrt_bc2 + a.eps;
-    p = p - a.lr_over_bc1 * (m / denom);
-}
-
-// CLIP = false is bbdm_adam_ema_step_f32, instruction for instruction what it was before the clipped entry point existed
-template <bool CLIP>
-__global__ void __launch_bounds__(256) adam_ema_kernel(const OptArgs a) {
-    const BbdmOptChunk c = a.table[blockIdx.x];
-    float* __restrict__ p = c.param;
-    const float* __restrict__ g = c.grad;
-    float* __restrict__ m = c.exp_avg;
-    float* __restrict__ v = c.exp_avg_sq;
-    float* __restrict__ s = c.shadow;
-    const int n = c.n;
-    bool adam = a.do_adam && g != nullptr;            // a parameter without a gradient is skipped, as torch does
-    float coef = 1.f;
-    if (CLIP) {
-        coef = a.clip[1];
-        if (a.skip_nonfinite && a.clip[2] == 0.f) adam = false;      // non-finite norm: p, m, v stay as they are
-    }
-    const bool ema = a.ema_mode != 0 && s != nullptr;
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)s;
-    if ((al & 15) == 0) {
-        const int n4 = n >> 2;
-        for (int i = threadIdx.x; i < n4; i += 256) {
-            float4 pv = reinterpret_cast<const float4*>(p)[i];
-            if (adam) {
-                float4 gv = reinterpret_cast<const float4*>(g)[i];
-                if (CLIP) { gv.x *= coef; gv.y *= coef; gv.z *= coef; gv.w *= coef; }
-                float4 mv = reinterpret_cast<const float4*>(m)[i];
-                float4 vv = reinterpret_cast<const float4*>(v)[i];
-                adam_one(a, pv.x, gv.x, mv.x, vv.x);
-                adam_one(a, pv.y, gv.y, mv.y, vv.y);
-                adam_one(a, pv.z, gv.z, mv.z, vv.z);
-                adam_one(a, pv.w, gv.w, mv.w, vv.w);
-                reinterpret_cast<float4*>(m)[i] = mv;
-                reinterpret_cast<float4*>(v)[i] = vv;
-                reinterpret_cast<float4*>(p)[i] = pv;
-            }
-            if (ema) {
-                float4 sv = pv;
-                if (a.ema_mode == 1) {
-                    const float4 o = reinterpret_cast<const float4*>(s)[i];
-                    sv.x = a.ema_c * pv.x + a.ema_decay * o.x;
-                    sv.y = a.ema_c * pv.y + a.ema_decay * o.y;
-                    sv.z = a.ema_c * pv.z + a.ema_decay * o.z;
-                    sv.w = a.ema_c * pv.w + a.ema_decay * o.w;
-                }
-                reinterpret_cast<float4*>(s)[i] = sv;
-            }
-        }
-        for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
-            float pv = p[i];
-            if (adam) {
-                float mv = m[i], vv = v[i];
-                adam_one(a, pv, CLIP ? g[i] * coef : g[i], mv, vv);
-                m[i] = mv; v[i] = vv; p[i] = pv;
-            }
-            if (ema) s[i] = a.ema_mode == 1 ? a.ema_c * pv + a.ema_decay * s[i] : pv;
-        }
-    } else {
-        for (int i = threadIdx.x; i < n; i += 256) {
-            float pv = p[i];
-            if (adam) {
-                float mv = m[i], vv = v[i];
-                adam_one(a, pv, CLIP ? g[i] * coef : g[i], mv, vv);
-                m[i] = mv; v[i] = vv; p[i] = pv;
-            }
-            if (ema) s[i] = a.ema_mode == 1 ? a.ema_c * pv + a.ema_decay * s[i] : pv;
-        }
-    }
-}
-
-// ---- the two other update rules of runners/utils.py:48-57 (RMSProp, SGD) on the same chunk table (ABI 30) ----------------------------
-// torch's single-tensor formulas (_single_tensor_sgd / _single_tensor_rmsprop), operation by operation.  An add with a Python-number
+// ---- the update rules of runners/utils.py:48-57 (Adam, RMSProp, SGD) on the same chunk table (ABI 30 added the last two) --------------
+// torch's single-tensor formulas (_single_tensor_adam / _sgd / _rmsprop), operation by operation.  An add with a Python-number
 // alpha (grad.add(param, alpha=wd), buf.add_(grad, alpha=1 - dampening), param.add_(grad, alpha=-lr)) is ONE rounding in ATen's CPU
-// kernels: fmaf here, as adam_one does for the weight decay; addcmul / addcdiv are written as adam_one writes them.
+// kernels: fmaf here; addcmul / addcdiv are written out.
+//   Adam     the header's four lines
 //   SGD      g' = g + wd * p;  buf = first ? g' : momentum * buf + (1 - dampening) * g';  g' = nesterov ? g' + momentum * buf : buf;
 //            p = p - lr * g'                                                  (the buf lines only with momentum != 0)
 //   RMSprop  g' = g + wd * p;  sq = alpha * sq + (1 - alpha) * g' * g';  avg = sqrt(sq) + eps;
 //            momentum != 0: buf = momentum * buf + g' / avg, p = p - lr * buf;  else p = p - lr * (g' / avg)
-// The table's exp_avg slot carries the momentum buffer (NULL without momentum), the exp_avg_sq slot RMSprop's square_avg (NULL for SGD).
-enum { RULE_SGD = 0, RULE_RMSPROP = 1 };
-
-struct RuleArgs {
-    const BbdmOptChunk* table;
-    float lr, wd, mom, damp_c, alpha, alpha_c, eps;              // damp_c = 1 - dampening, alpha_c = 1 - alpha
-    float ema_decay, ema_c;
-    int nesterov, first, ema_mode;                                // first: SGD's first step with momentum: buf = g' (buf is not read)
-    const float* clip;                                            // rule_ema_kernel<.., .., true>: {norm, coef, ok, 0}
-    int skip_nonfinite;
-};
-
+// The table's exp_avg slot carries Adam's first moment or the momentum buffer (NULL without momentum), the exp_avg_sq slot Adam's second
+// moment or RMSprop's square_avg (NULL for SGD).
 template <int RULE, bool MOM>
-__device__ __forceinline__ void rule_one(const RuleArgs& a, float& p, float g, float& buf, float& sq) {
-    if (a.wd != 0.f) g = fmaf(a.wd, p, g);
-    if (RULE == RULE_SGD) {
+__device__ __forceinline__ void rule_one(const OptArgs& a, float& p, float g, float& buf, float& sq) {
+    if (a.wd != 0.f) g = fmaf(a.wd, p, g);          // grad.add(param, alpha=wd): one rounding in ATen's kernels
+    if (RULE == RULE_ADAM) {
+        // at::lerp: |w| < 0.5 ? a + w (b - a) : b - (b - a) (1 - w),  w = 1 - beta1
+        buf = a.b1c < 0.5f ? buf + a.b1c * (g - buf) : g - (g - buf) * (1.f - a.b1c);
+        sq = sq * a.b2 + a.b2c * g * g;
+        const float denom = sqrtf(sq) / a.sqrt_bc2 + a.eps;
+        p = p - a.lr * (buf / denom);
+    } else if (RULE == RULE_SGD) {
         if (MOM) {
             buf = a.first ? g : fmaf(a.damp_c, g, a.mom * buf);
             g = a.nesterov ? fmaf(a.mom, buf, g) : buf;
@@ -174,19 +101,61 @@ __device__ __forceinline__ void rule_one(const RuleArgs& a, float& p, float g, f
     }
 }
 
-// adam_ema_kernel's mapping and access widths; MOM: the rule reads / writes the momentum buffer, RULE_RMSPROP: square_avg.  A chunk
-// whose gradient, or a state tensor the rule needs, is NULL gets no update (its EMA part still runs).
-template <int RULE, bool MOM, bool CLIP>
-__global__ void __launch_bounds__(256) rule_ema_kernel(const RuleArgs a) {
-    constexpr bool SQ = RULE == RULE_RMSPROP;
+// EMA.update (runners/base/EMA.py:21-29): shadow = (1 - d) * p + d * shadow
+__device__ __forceinline__ float ema_blend(const OptArgs& a, float p, float shadow) { return a.ema_c * p + a.ema_decay * shadow; }
+
+// W consecutive floats of a chunk: one 128-bit access (W = 4, i counts groups of four) or one element (W = 1, i counts elements).
+template <int W>
+struct Lanes {
+    float v[W];
+};
+
+template <int W>
+__device__ __forceinline__ Lanes<W> load_lanes(const float* p, int i) {
+    Lanes<W> r;
+    if constexpr (W == 4) {
+        const float4 f = reinterpret_cast<const float4*>(p)[i];
+        r.v[0] = f.x, r.v[1] = f.y, r.v[2] = f.z, r.v[3] = f.w;
+    } else {
+        r.v[0] = p[i];
+    }
+    return r;
+}
+
+template <int W>
+__device__ __forceinline__ void store_lanes(float* p, int i, const Lanes<W>& r) {
+    if constexpr (W == 4) reinterpret_cast<float4*>(p)[i] = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    else p[i] = r.v[0];
+}
+
+// The walk of one workgroup over its chunk of n elements: f(int_tag<4>, i) for thread-strided groups of four and then f(int_tag<1>, i)
+// for the tail's elements when every pointer f touches is 16-byte aligned (`aligned`), else f(int_tag<1>, i) for all of the chunk.
+template <class F>
+__device__ __forceinline__ void chunk_walk(int n, bool aligned, F f) {
+    int done = 0;
+    if (aligned) {
+        const int n4 = n >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) f(int_tag<4>{}, i);
+        done = n4 << 2;
+    }
+    for (int i = done + threadIdx.x; i < n; i += 256) f(int_tag<1>{}, i);
+}
+
+// One rule's update and the EMA part over one chunk per workgroup.  MOM: the rule reads / writes the exp_avg slot (Adam always),
+// UPDATE = false: the EMA part alone, whatever the table holds (Adam's do_adam = 0), CLIP: g * coef (one rounding, as grads.mul_(coef))
+// in front of the rule; ok == 0 under skip_nonfinite: no update (the EMA part still runs, as the runner's ema.update would).  A chunk
+// whose gradient, or a state tensor the rule needs, is NULL gets no update either: a parameter without a gradient is skipped, as torch
+// does.
+template <int RULE, bool MOM, bool UPDATE, bool CLIP>
+__global__ void __launch_bounds__(256) rule_ema_kernel(const OptArgs a) {
+    constexpr bool SQ = RULE != RULE_SGD;
     const BbdmOptChunk c = a.table[blockIdx.x];
     float* __restrict__ p = c.param;
     const float* __restrict__ g = c.grad;
     float* __restrict__ m = c.exp_avg;
     float* __restrict__ v = c.exp_avg_sq;
     float* __restrict__ s = c.shadow;
-    const int n = c.n;
-    bool upd = g != nullptr && (!MOM || m != nullptr) && (!SQ || v != nullptr);
+    bool upd = UPDATE && g != nullptr && (!MOM || m != nullptr) && (!SQ || v != nullptr);
     float coef = 1.f;
     if (CLIP) {
         coef = a.clip[1];
@@ -197,49 +166,30 @@ __global__ void __launch_bounds__(256) rule_ema_kernel(const RuleArgs a) {
     uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)s;
     if (MOM) al |= (uintptr_t)m;
     if (SQ) al |= (uintptr_t)v;
-    if ((al & 15) == 0) {
-        const int n4 = n >> 2;
-        for (int i = threadIdx.x; i < n4; i += 256) {
-            float4 pv = reinterpret_cast<const float4*>(p)[i];
-            if (upd) {
-                float4 gv = reinterpret_cast<const float4*>(g)[i];
-                if (CLIP) { gv.x *= coef; gv.y *= coef; gv.z *= coef; gv.w *= coef; }
-                float4 mv = make_float4(0.f, 0.f, 0.f, 0.f), vv = mv;
-                if (rd_m) mv = reinterpret_cast<const float4*>(m)[i];
-                if (SQ) vv = reinterpret_cast<const float4*>(v)[i];
-                rule_one<RULE, MOM>(a, pv.x, gv.x, mv.x, vv.x);
-                rule_one<RULE, MOM>(a, pv.y, gv.y, mv.y, vv.y);
-                rule_one<RULE, MOM>(a, pv.z, gv.z, mv.z, vv.z);
-                rule_one<RULE, MOM>(a, pv.w, gv.w, mv.w, vv.w);
-                if (MOM) reinterpret_cast<float4*>(m)[i] = mv;
-                if (SQ) reinterpret_cast<float4*>(v)[i] = vv;
-                reinterpret_cast<float4*>(p)[i] = pv;
-            }
-            if (ema) {
-                float4 sv = pv;
-                if (a.ema_mode == 1) {
-                    const float4 o = reinterpret_cast<const float4*>(s)[i];
-                    sv.x = a.ema_c * pv.x + a.ema_decay * o.x;
-                    sv.y = a.ema_c * pv.y + a.ema_decay * o.y;
-                    sv.z = a.ema_c * pv.z + a.ema_decay * o.z;
-                    sv.w = a.ema_c * pv.w + a.ema_decay * o.w;
-                }
-                reinterpret_cast<float4*>(s)[i] = sv;
-            }
-        }
-    }
-    // element accesses: the tail of an aligned chunk, or all of an unaligned one
-    for (int i = ((al & 15) == 0 ? (n >> 2) << 2 : 0) + threadIdx.x; i < n; i += 256) {
-        float pv = p[i];
+    chunk_walk(c.n, (al & 15) == 0, [&](auto W, int i) {
+        constexpr int w = decltype(W)::value;
+        Lanes<w> pv = load_lanes<w>(p, i);
         if (upd) {
-            float mv = rd_m ? m[i] : 0.f, vv = SQ ? v[i] : 0.f;
-            rule_one<RULE, MOM>(a, pv, CLIP ? g[i] * coef : g[i], mv, vv);
-            if (MOM) m[i] = mv;
-            if (SQ) v[i] = vv;
-            p[i] = pv;
+            const Lanes<w> gv = load_lanes<w>(g, i);
+            Lanes<w> mv = {}, vv = {};
+            if (rd_m) mv = load_lanes<w>(m, i);
+            if (SQ) vv = load_lanes<w>(v, i);
+#pragma unroll
+            for (int j = 0; j < w; ++j) rule_one<RULE, MOM>(a, pv.v[j], CLIP ? gv.v[j] * coef : gv.v[j], mv.v[j], vv.v[j]);
+            if (MOM) store_lanes<w>(m, i, mv);
+            if (SQ) store_lanes<w>(v, i, vv);
+            store_lanes<w>(p, i, pv);
         }
-        if (ema) s[i] = a.ema_mode == 1 ? a.ema_c * pv + a.ema_decay * s[i] : pv;
-    }
+        if (ema) {
+            Lanes<w> sv = pv;
+            if (a.ema_mode == 1) {
+                const Lanes<w> o = load_lanes<w>(s, i);
+#pragma unroll
+                for (int j = 0; j < w; ++j) sv.v[j] = ema_blend(a, pv.v[j], o.v[j]);
+            }
+            store_lanes<w>(s, i, sv);
+        }
+    });
 }
 
 constexpr int NORM_CELLS = 256;          // accumulator cells of the squared norm, one per 128-byte line
@@ -322,57 +272,63 @@ __global__ void __launch_bounds__(256) grad_scale_kernel(const BbdmOptChunk* __r
     float* __restrict__ g = const_cast<float*>(c.grad);
     if (g == nullptr) return;
     const float coef = clip[1];
-    const int n = c.n;
-    if (((uintptr_t)g & 15) == 0) {
-        const int n4 = n >> 2;
-        for (int i = threadIdx.x; i < n4; i += 256) {
-            float4 v = reinterpret_cast<float4*>(g)[i];
-            v.x *= coef; v.y *= coef; v.z *= coef; v.w *= coef;
-            reinterpret_cast<float4*>(g)[i] = v;
-        }
-        for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) g[i] *= coef;
-    } else {
-        for (int i = threadIdx.x; i < n; i += 256) g[i] *= coef;
-    }
+    chunk_walk(c.n, ((uintptr_t)g & 15) == 0, [&](auto W, int i) {
+        constexpr int w = decltype(W)::value;
+        Lanes<w> v = load_lanes<w>(g, i);
+#pragma unroll
+        for (int j = 0; j < w; ++j) v.v[j] *= coef;
+        store_lanes<w>(g, i, v);
+    });
 }
 
 }  // namespace
 
 extern "C" int bbdm_opt_chunk_elems(void) { return CHUNK; }
 
+// What every rule's launcher starts with: the shared checks and fields, every other field zero.  Hyper-parameters arrive as the Python
+// doubles torch works with; every derived scalar (lr / bc1, 1 - beta, 1 - dampening, 1 - alpha, 1 - decay) is formed in double and rounded
+// to fp32 once, which is what a Python-number operand of an fp32 tensor op undergoes.
+static int opt_args_common(OptArgs& a, const char* what, const BbdmOptChunk* table, int nchunks, double lr, double weight_decay,
+                           int ema_mode, double ema_decay, const float* clip, int skip_nonfinite) {
+    BBDM_REQUIRE(table && nchunks > 0, "%s: empty chunk table", what);
+    BBDM_REQUIRE(ema_mode >= 0 && ema_mode <= 2, "%s: ema_mode=%d (0 none, 1 decay, 2 copy)", what, ema_mode);
+    a = OptArgs{};
+    a.table = table;
+    a.lr = (float)lr;
+    a.wd = (float)weight_decay;
+    a.ema_decay = (float)ema_decay;
+    a.ema_c = (float)(1.0 - ema_decay);
+    a.ema_mode = ema_mode;
+    a.clip = clip;
+    a.skip_nonfinite = skip_nonfinite;
+    return BBDM_OK;
+}
+
+template <int RULE, bool MOM, bool UPDATE, bool CLIP>
+static int rule_ema_launch(const OptArgs& a, int nchunks, void* stream, const char* what) {
+    hipLaunchKernelGGL((rule_ema_kernel<RULE, MOM, UPDATE, CLIP>), dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, a);
+    BBDM_CHECK_LAUNCH(what);
+    return BBDM_OK;
+}
+
 static int adam_ema_launch(const BbdmOptChunk* table, int nchunks, int do_adam, double lr, double beta1, double beta2, double eps,
                            double weight_decay, long long step, int ema_mode, double ema_decay, const float* clip,
                            int skip_nonfinite, void* stream) {
-    BBDM_REQUIRE(table && nchunks > 0, "adam_ema: empty chunk table");
-    BBDM_REQUIRE(do_adam || ema_mode, "adam_ema: nothing to do");
-    BBDM_REQUIRE(ema_mode >= 0 && ema_mode <= 2, "adam_ema: ema_mode=%d (0 none, 1 decay, 2 copy)", ema_mode);
-    BBDM_REQUIRE(!do_adam || (step >= 1 && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0.),
-                 "adam_ema: bad hyper-parameters (step=%lld beta1=%g beta2=%g eps=%g)", step, beta1, beta2, eps);
     OptArgs a;
-    a.table = table;
-    // hyper-parameters arrive as the Python doubles torch works with; every derived scalar is formed in double and
-    // rounded to fp32 once, which is what a Python-number operand of an fp32 tensor op undergoes
     const double bc1 = do_adam ? 1.0 - pow(beta1, (double)step) : 1.0;
     const double bc2 = do_adam ? 1.0 - pow(beta2, (double)step) : 1.0;
-    a.lr_over_bc1 = (float)(lr / bc1);
+    if (const int rc = opt_args_common(a, "adam_ema", table, nchunks, lr / bc1, weight_decay, ema_mode, ema_decay, clip, skip_nonfinite))
+        return rc;
+    BBDM_REQUIRE(do_adam || ema_mode, "adam_ema: nothing to do");
+    BBDM_REQUIRE(!do_adam || (step >= 1 && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0.),
+                 "adam_ema: bad hyper-parameters (step=%lld beta1=%g beta2=%g eps=%g)", step, beta1, beta2, eps);
     a.sqrt_bc2 = (float)sqrt(bc2);
     a.b1c = (float)(1.0 - beta1);
     a.b2 = (float)beta2;
     a.b2c = (float)(1.0 - beta2);
     a.eps = (float)eps;
-    a.wd = (float)weight_decay;
-    a.ema_decay = (float)ema_decay;
-    a.ema_c = (float)(1.0 - ema_decay);
-    a.do_adam = do_adam;
-    a.ema_mode = ema_mode;
-    a.clip = clip;
-    a.skip_nonfinite = skip_nonfinite;
-    if (clip != nullptr)
-        hipLaunchKernelGGL(adam_ema_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(adam_ema_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, a);
-    BBDM_CHECK_LAUNCH("adam_ema");
-    return BBDM_OK;
+    return dispatch([&](auto UPDATE, auto CLIP) { return rule_ema_launch<RULE_ADAM, true, UPDATE(), CLIP()>(a, nchunks, stream, "adam_ema"); },
+                    do_adam != 0, clip != nullptr);
 }
 
 extern "C" int bbdm_adam_ema_step_f32(const BbdmOptChunk* table, int nchunks, int do_adam, double lr, double beta1,
@@ -389,44 +345,27 @@ extern "C" int bbdm_adam_ema_step_clip_f32(const BbdmOptChunk* table, int nchunk
                            skip_nonfinite != 0, stream);
 }
 
-template <int RULE>
-static void rule_ema_dispatch(const RuleArgs& a, int nchunks, void* stream) {
-    const dim3 grid((unsigned)nchunks), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (a.mom != 0.f) {
-        if (a.clip != nullptr) hipLaunchKernelGGL((rule_ema_kernel<RULE, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((rule_ema_kernel<RULE, true, false>), grid, block, 0, st, a);
-    } else {
-        if (a.clip != nullptr) hipLaunchKernelGGL((rule_ema_kernel<RULE, false, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((rule_ema_kernel<RULE, false, false>), grid, block, 0, st, a);
-    }
-}
-
-// hyper-parameters arrive as Python doubles and are rounded to fp32 once, after any host arithmetic (1 - dampening, 1 - alpha), as in
-// adam_ema_launch
-static int rule_ema_common(RuleArgs& a, const BbdmOptChunk* table, int nchunks, double lr, double weight_decay, double momentum,
+// SGD and RMSprop: the checks and fields the two share
+static int rule_ema_common(OptArgs& a, const BbdmOptChunk* table, int nchunks, double lr, double weight_decay, double momentum,
                            int ema_mode, double ema_decay, const float* clip, int skip_nonfinite, const char* what) {
-    BBDM_REQUIRE(table && nchunks > 0, "%s: empty chunk table", what);
-    BBDM_REQUIRE(ema_mode >= 0 && ema_mode <= 2, "%s: ema_mode=%d (0 none, 1 decay, 2 copy)", what, ema_mode);
+    if (const int rc = opt_args_common(a, what, table, nchunks, lr, weight_decay, ema_mode, ema_decay, clip, skip_nonfinite)) return rc;
     BBDM_REQUIRE(lr >= 0. && weight_decay >= 0. && momentum >= 0., "%s: bad hyper-parameters (lr=%g weight_decay=%g momentum=%g)", what,
                  lr, weight_decay, momentum);
-    a.table = table;
-    a.lr = (float)lr;
-    a.wd = (float)weight_decay;
     a.mom = (float)momentum;
-    a.damp_c = 1.f; a.alpha = 0.f; a.alpha_c = 1.f; a.eps = 0.f;
-    a.nesterov = 0; a.first = 0;
-    a.ema_decay = (float)ema_decay;
-    a.ema_c = (float)(1.0 - ema_decay);
-    a.ema_mode = ema_mode;
-    a.clip = clip;
-    a.skip_nonfinite = skip_nonfinite;
+    a.damp_c = 1.f;
+    a.alpha_c = 1.f;
     return BBDM_OK;
+}
+
+template <int RULE>
+static int rule_ema_dispatch(const OptArgs& a, int nchunks, void* stream, const char* what) {
+    return dispatch([&](auto MOM, auto CLIP) { return rule_ema_launch<RULE, MOM(), true, CLIP()>(a, nchunks, stream, what); },
+                    a.mom != 0.f, a.clip != nullptr);
 }
 
 static int sgd_ema_launch(const BbdmOptChunk* table, int nchunks, double lr, double momentum, double dampening, double weight_decay,
                           int nesterov, int first, int ema_mode, double ema_decay, const float* clip, int skip_nonfinite, void* stream) {
-    RuleArgs a;
+    OptArgs a;
     const int rc = rule_ema_common(a, table, nchunks, lr, weight_decay, momentum, ema_mode, ema_decay, clip, skip_nonfinite, "sgd_ema");
     if (rc != BBDM_OK) return rc;
     BBDM_REQUIRE(!nesterov || (momentum > 0. && dampening == 0.), "sgd_ema: nesterov needs momentum > 0 and dampening == 0 (momentum=%g "
@@ -434,14 +373,12 @@ static int sgd_ema_launch(const BbdmOptChunk* table, int nchunks, double lr, dou
     a.damp_c = (float)(1.0 - dampening);
     a.nesterov = nesterov != 0;
     a.first = first != 0;
-    rule_ema_dispatch<RULE_SGD>(a, nchunks, stream);
-    BBDM_CHECK_LAUNCH("sgd_ema");
-    return BBDM_OK;
+    return rule_ema_dispatch<RULE_SGD>(a, nchunks, stream, "sgd_ema");
 }
 
 static int rmsprop_ema_launch(const BbdmOptChunk* table, int nchunks, double lr, double alpha, double eps, double weight_decay,
                               double momentum, int ema_mode, double ema_decay, const float* clip, int skip_nonfinite, void* stream) {
-    RuleArgs a;
+    OptArgs a;
     const int rc = rule_ema_common(a, table, nchunks, lr, weight_decay, momentum, ema_mode, ema_decay, clip, skip_nonfinite,
                                    "rmsprop_ema");
     if (rc != BBDM_OK) return rc;
@@ -449,9 +386,7 @@ static int rmsprop_ema_launch(const BbdmOptChunk* table, int nchunks, double lr,
     a.alpha = (float)alpha;
     a.alpha_c = (float)(1.0 - alpha);
     a.eps = (float)eps;
-    rule_ema_dispatch<RULE_RMSPROP>(a, nchunks, stream);
-    BBDM_CHECK_LAUNCH("rmsprop_ema");
-    return BBDM_OK;
+    return rule_ema_dispatch<RULE_RMSPROP>(a, nchunks, stream, "rmsprop_ema");
 }
 
 extern "C" int bbdm_sgd_ema_step_f32(const BbdmOptChunk* table, int nchunks, double lr, double momentum, double dampening,

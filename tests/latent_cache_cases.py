@@ -103,6 +103,48 @@ def kernel_equals_unfused(dev, shape, off, philox):
     assert checked == 18
 
 
+def ragged_group_follows_the_formula(dev, philox):
+    """1b. The element route with a ragged last group (N = 3, per_sample = hw = 7, statistics on) against torch fp32 tensor ops in
+    the reference's order: (z - mean) / std (LatentBrownianBridgeModel.py:92-97), then q_sample (BrownianBridgeModel.py:128-146).
+
+    Bound.  The kernel evaluates the same IEEE fp32 operations (no contraction; the division and sqrtf are correctly rounded by
+    default), so the results differ at most by a last-place difference of the division or the square root: 2^-23 of a term each.
+    y_out is one subtraction and one division: <= 2 * 2^-23 relative.  x_t and the target take two such rows and sqrt(var):
+    <= 8 * 2^-23 * S elementwise, S the sum of the terms' absolute values."""
+    from bbdm_amd import philox_normal
+    g = torch.Generator().manual_seed(33)
+    M, N, shape = 4, 3, (1, 7)
+    ori, cond, noise = torch.randn((M,) + shape, generator=g), torch.randn((M,) + shape, generator=g), torch.randn((N,) + shape, generator=g)
+    io, ic, t = [2, 0, 3], [1, 3, 0], [0, 999, 412]
+    stats = [torch.tensor([v], dtype=torch.float32) for v in (0.3, 1.7, -0.35, 0.75)]
+    m_t, var_t = _tables(dev)
+    seed = torch.tensor([1, 2 ** 35 + 2, -4], dtype=torch.int64, device=dev)
+    ordinal = torch.tensor([0, 2 ** 32 + 1, 17], dtype=torch.int64, device=dev)
+    if philox:
+        noise = philox_normal(shape, seed, ordinal, domain=1).cpu()
+    src = (seed, ordinal) if philox else (noise.to(dev),)
+    m = m_t.cpu()[t].view(N, 1, 1)
+    sig = torch.sqrt(var_t.cpu()[t]).view(N, 1, 1)
+    a, b = (ori[io] - stats[0]) / stats[1], (cond[ic] - stats[2]) / stats[3]
+    eps = 2.0 ** -23
+    for objective in (0, 1, 2):
+        got = [torch.full((N,) + shape, SENTINEL, device=dev) for _ in range(3)]
+        _cached(philox, ori.to(dev), cond.to(dev), *(torch.tensor(v, dtype=torch.int64, device=dev) for v in (io, ic)),
+                [s.to(dev) for s in stats], 7, src, torch.tensor(t, dtype=torch.int64, device=dev), m_t, var_t, objective, got)
+        x_t, target, y_out = (o.cpu() for o in got)
+        ref_x, s_x = (1.0 - m) * a + m * b + sig * noise, (1.0 - m) * a.abs() + m * b.abs() + sig * noise.abs()
+        if objective == 0:
+            ref_t, s_t = m * (b - a) + sig * noise, m * (b.abs() + a.abs()) + sig * noise.abs()
+        elif objective == 1:
+            ref_t, s_t = noise, noise.abs()
+        else:
+            ref_t, s_t = b - a, b.abs() + a.abs()
+        ey = float(((y_out - b).abs() / b.abs()).max())
+        ex, et = float(((x_t - ref_x).abs() / s_x).max()), float(((target - ref_t).abs() / s_t).max())
+        print(f"objective {objective} philox {philox}: y_out {ey / eps:.2f}, x_t {ex / eps:.2f}, target {et / eps:.2f} x 2^-23 (bars 2, 8, 8)")
+        assert ey <= 2 * eps and ex <= 8 * eps and et <= 8 * eps, (objective, ey, ex, et)
+
+
 def out_of_range_rows_are_nan(dev, shape, off, philox):
     """2. Indices -1 and M: NaN rows in all three outputs for those images, every other image bit-equal to the in-range run."""
     ori, cond, noise, t, seed, ordinal, stats = _kernel_inputs(dev, shape, off)

@@ -112,3 +112,24 @@ def ema_parity(dev):
         ea.update(a)
     ea.restore(a)
     assert {k: p.data_ptr() for k, p in a.named_parameters()} == before and ea.backup == {}
+
+
+def ema_copy_leaves_gradient_rows_alone(dev):
+    """bbdm_adam_ema_step_f32 with do_adam = 0 and ema_mode = 2 on a table whose rows CARRY gradients and both moments (an aligned row
+    of 16 390 elements: a full chunk and a tail; a 3-element row; a row one float past an alignment): parameters, gradients and
+    moments keep their bits, every shadow becomes its parameter, bit for bit."""
+    from bbdm_amd import _lib
+    from bbdm_amd.optim import _ChunkTable
+    g = torch.Generator().manual_seed(23)
+    rows = []
+    for n, off in ((16390, 0), (3, 0), (16390, 1)):
+        rows.append(tuple(torch.randn(n + off, generator=g).to(dev)[off:] for _ in range(5)))
+    assert rows[2][0].data_ptr() % 16 != 0
+    before = [[x.clone() for x in r] for r in rows]
+    table, n = _ChunkTable().get(rows, dev)
+    with _lib.device_guard(dev):
+        _lib.call("bbdm_adam_ema_step_f32", table.data_ptr(), n, 0, 1e-3, 0.9, 0.999, 1e-8, 0.01, 1, 2, 0.995, _lib.current_stream(dev))
+    for (p, gr, m, v, s), old in zip(rows, before):
+        for x, o in zip((p, gr, m, v), old):
+            assert torch.equal(x, o)
+        assert torch.equal(s, p) and not torch.equal(s, old[4])

@@ -210,6 +210,68 @@ def fused_step_equals_unfused(dev, shape, off):
     assert checked == 12 * 3 * 4
 
 
+def step_formula(x, y, pred, z, m_t, var_t, t, t_next, last, eta, clip, objective):
+    """One image's bridge step as torch fp32 tensor ops in the reference's order (BrownianBridgeModel.py:148-160, 186-201), on the
+    CPU -> (x_next, x0_recon, S_next, S_0): S_* = the sum of the absolute values of the terms each result is formed from."""
+    m, var = m_t[t], var_t[t]
+    sig = torch.sqrt(var)
+    if objective == 0:
+        x0, s0 = x - pred, x.abs() + pred.abs()
+    elif objective == 1:
+        x0, s0 = (x - m * y - sig * pred) / (1.0 - m), (x.abs() + m * y.abs() + sig * pred.abs()) / (1.0 - m)
+    else:
+        x0, s0 = y - pred, y.abs() + pred.abs()
+    if clip:
+        x0 = x0.clamp(-1.0, 1.0)
+    if last:
+        return x0, x0, s0, s0
+    m_nt, var_nt = m_t[t_next], var_t[t_next]
+    sigma2 = (var - var_nt * (1.0 - m) ** 2 / (1.0 - m_nt) ** 2) * var_nt / var
+    sigma_t = torch.sqrt(sigma2) * eta
+    coef = torch.sqrt((var_nt - sigma2) / var)
+    xn = (1.0 - m_nt) * x0 + m_nt * y + coef * (x - (1.0 - m) * x0 - m * y) + sigma_t * z
+    sn = (1.0 - m_nt) * s0 + m_nt * y.abs() + coef * (x.abs() + (1.0 - m) * s0 + m * y.abs()) + sigma_t * z.abs()
+    return xn, x0, sn, s0
+
+
+def fused_step_follows_the_formula(dev):
+    """The element route of the Philox step kernel with a ragged last group (N = 3, per_sample = 7: one group of four, one of three)
+    against step_formula on philox_normal's tensor: a noisy step, a last step and an idle slot; 3 objectives x clip {0, 1}.
+
+    Bound.  The kernel and step_formula evaluate the same sequence of IEEE fp32 operations (no contraction; HIP rounds sqrtf and the
+    division correctly by default), so the results agree up to a last-place difference of a sqrt or a division where a library takes
+    another route: two such operations feed x0_recon, five more feed x_next, each a relative 2^-23 of a term.  Hence
+    |x0 - ref| <= 4 * 2^-23 * S_0 and |x_next - ref| <= 16 * 2^-23 * S_next elementwise (S_*: the sum of the terms' absolute values,
+    the perturbation of x0 carried through its coefficients).  A wrong coefficient or a wrong element of the tail is not a
+    last-place difference."""
+    from bbdm_amd import bridge_schedule, philox_normal
+    tables, _ = bridge_schedule(1000, "linear", 1.0, True, "linear", 200)
+    m_c, var_c = (torch.tensor(tables[k], dtype=torch.float32) for k in ("m_t", "variance_t"))
+    g = torch.Generator().manual_seed(17)
+    N, shape = 3, (7,)
+    x, y, pred = (torch.randn((N,) + shape, generator=g) for _ in range(3))
+    t, t_next, flag = [494, 0, 37], [489, 0, 32], [0, 1, 2]
+    seed = torch.tensor([5, 2 ** 33 + 1, 77], dtype=torch.int64, device=dev)
+    ordinal = torch.tensor([0, 101, 7], dtype=torch.int64, device=dev)
+    z = philox_normal(shape, seed, ordinal, domain=0).cpu()
+    dx, dy, dp = (a.to(dev) for a in (x, y, pred))
+    assert dx[0].numel() % 4 != 0
+    dt, dn, df = (torch.tensor(v, dtype=torch.int64, device=dev) for v in (t, t_next, flag))
+    eps = 2.0 ** -23
+    for objective in (0, 1, 2):
+        for clip in (0, 1):
+            got = [torch.full_like(dx, S.SENTINEL) for _ in range(3)]
+            _philox_step(dx, dy, dp, seed, ordinal, m_c.to(dev), var_c.to(dev), dt, dn, df, 1.0, clip, objective, *got)
+            xn, x0, alias = (a.cpu() for a in got)
+            assert torch.equal(xn, alias)
+            assert bool((xn[2] == S.SENTINEL).all()) and bool((x0[2] == S.SENTINEL).all())
+            for n in (0, 1):
+                rn, r0, sn, s0 = step_formula(x[n], y[n], pred[n], z[n], m_c, var_c, t[n], t_next[n], flag[n] == 1, 1.0, clip, objective)
+                e0, en = float(((x0[n] - r0).abs() / s0).max()), float(((xn[n] - rn).abs() / sn).max())
+                print(f"objective {objective} clip {clip} image {n}: x0_recon {e0 / eps:.2f} x 2^-23 (bar 4), x_next {en / eps:.2f} x 2^-23 (bar 16)")
+                assert e0 <= 4 * eps and en <= 16 * eps, (objective, clip, n, e0, en)
+
+
 def fused_q_sample_equals_unfused(dev, shape, off):
     """4. (q_sample) bbdm_bb_q_sample_philox_f32 equals bbdm_bb_q_sample_f32 fed philox_normal(domain=1): x_t and target, all three
     objectives, bitwise."""

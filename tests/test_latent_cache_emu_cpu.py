@@ -55,3 +55,8 @@ def test_float_inputs_keep_their_path_after_attach():
 
 def test_cached_pairs_feed_the_runner_loss_fn():
     L.runner_seam(CPU)
+
+
+@NOISE
+def test_cached_q_sample_with_a_ragged_group_follows_the_formula(philox):
+    L.ragged_group_follows_the_formula(CPU, philox)

@@ -40,3 +40,8 @@ def test_training_step_on_indices_equals_the_step_on_images(dev, monkeypatch, no
 
 def test_float_inputs_keep_their_path_after_attach(dev):
     L.float_inputs_keep_their_path(dev)
+
+
+@NOISE
+def test_cached_q_sample_with_a_ragged_group_follows_the_formula(dev, philox):
+    L.ragged_group_follows_the_formula(dev, philox)

@@ -22,3 +22,7 @@ def test_fused_adam_matches_torch_adam(wd, beta1):
 
 def test_ema_matches_reference_ema_and_fuses_into_the_step():
     C.ema_parity(CPU)
+
+
+def test_ema_copy_without_adam_leaves_rows_that_carry_gradients_alone():
+    C.ema_copy_leaves_gradient_rows_alone(CPU)

@@ -70,3 +70,7 @@ def test_full_size_step_one_launch_and_rate(dev):
     print(f"fused Adam+EMA over {n / 1e6:.1f} M parameters: {ms:.3f} ms/step = {9 * 4 * n / ms / 1e9:.2f} TB/s "
           f"(torch.optim.Adam alone: {t0.elapsed_time(t1) / 5:.3f} ms); worst rel err {worst:.2e}")
     assert worst < 1e-6
+
+
+def test_ema_copy_without_adam_leaves_rows_that_carry_gradients_alone(dev):
+    C.ema_copy_leaves_gradient_rows_alone(dev)

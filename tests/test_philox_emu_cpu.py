@@ -39,3 +39,7 @@ def test_fused_q_sample_equals_q_sample_fed_the_noise_tensor(shape, off):
 
 def test_philox_sampler_and_model_sample_follow_the_oracle():
     P.model_level(CPU, hip_graph=False, extras=False)
+
+
+def test_fused_step_with_a_ragged_group_follows_the_formula():
+    P.fused_step_follows_the_formula(CPU)

@@ -60,3 +60,7 @@ def test_philox_sampler_issues_no_normal_launch_and_is_reproducible(dev):
     b = dict(s)
     for k in range(3):
         assert torch.equal(a[k], b[k])
+
+
+def test_fused_step_with_a_ragged_group_follows_the_formula(dev):
+    P.fused_step_follows_the_formula(dev)

@@ -10,6 +10,8 @@ GPU builds: the child runs with BBDM_HIP_LIB = the library.  --emu: both are bui
 _lib.bind(path).  The grid is the product of each launcher's routing conditions at the smallest shapes that reach the route; a call
 that the library rejects is recorded with its error text (and must be rejected alike by both).  Routes that differ only in index
 width give equal bits by design and are run all the same: a wrong route that leaves its buffers shows on the emulator's bounds.
+The elementwise files (bridge.hip, optim.hip, loss_meter.hip; built without FMA contraction, so a refactor of their KERNELS keeps every
+bit as well) are covered entry point by entry point: elementwise_grid().
 """
 import argparse
 import ctypes
@@ -397,6 +399,302 @@ def linear_case(c, N, In, Out, packed):
     return [y]
 
 
+# ---- the elementwise files (bridge.hip, optim.hip, loss_meter.hip): every entry point, at the smallest shapes that reach each route --------
+def ints(c, vals):
+    return c.torch.tensor(vals, dtype=c.torch.int64).to(c.dev)
+
+
+def floats(c, vals):
+    return c.torch.tensor(vals, dtype=c.torch.float32).to(c.dev)
+
+
+def rand_off(c, seed, n, off, scale=1.0):
+    """n seeded floats that start `off` floats past an allocation (off = 1: no pointer is 16-byte aligned)."""
+    return c.rand(seed, n + off, scale=scale)[off:]
+
+
+def zeros_off(c, n, off):
+    return c.zeros(n + off)[off:]
+
+
+def per_image(c, vals, N):
+    """An int64 value per image: `vals` repeated to N entries."""
+    return ints(c, (vals * (N // len(vals) + 1))[:N])
+
+
+def schedule(c, T=10):
+    """m_t rising from 0.001 to 0.999 and the bridge's variance 2 (m - m^2), as BrownianBridgeModel.register_schedule forms them."""
+    m = c.torch.linspace(0.001, 0.999, T, dtype=c.torch.float32)
+    return m.to(c.dev), (2.0 * (m - m * m)).to(c.dev)
+
+
+# (per_sample, offset): a ragged last group; two blocks in x on 16-byte accesses; the same on element accesses with every group full
+IMAGE_SHAPES = {"tail": (7, 0), "vec": (1032, 0), "elem": (1032, 1)}
+
+
+def p_step_image_case(c, form, shape, objective, clip, alias, N=3):
+    """The four per-image step entries.  States 0, 1, 2 over the three images; the request forms carry clip in bit 2 and eta per image."""
+    ps, off = IMAGE_SHAPES.get(shape, (shape, 0))
+    requests, philox = "requests" in form, "philox" in form
+    n = max(N * ps, 1)                                    # (per_sample = 0 is refused before any access; no pointer may be null)
+    x_t, y, pred = rand_off(c, 201, n, off), rand_off(c, 202, n, off), rand_off(c, 203, n, off)
+    m_tab, var_tab = schedule(c)
+    t, t_next = per_image(c, [7, 4, 1], N), per_image(c, [5, 2, 0], N)
+    flag = per_image(c, [4, 5, 2] if requests and clip else [0, 1, 2], N)
+    x_next, x0 = zeros_off(c, n, off), zeros_off(c, n, off)
+    al = zeros_off(c, n, off) if alias else None
+    src = (per_image(c, [11, 12, 13], N), per_image(c, [0, 5, 2 ** 33], N)) if philox else (rand_off(c, 204, n, off),)
+    eta = floats(c, ([1.0, 0.5, 0.25] * (N // 3 + 1))[:N])
+    par = (P(eta),) if requests else (0.75, clip)
+    name = {"batched": "bbdm_bb_p_sample_step_batched_f32", "requests": "bbdm_bb_p_sample_step_requests_f32",
+            "philox": "bbdm_bb_p_sample_step_philox_f32", "requests_philox": "bbdm_bb_p_sample_step_requests_philox_f32"}[form]
+    c.call(name, P(x_t), P(y), P(pred), *map(P, src), P(m_tab), P(var_tab), P(t), P(t_next), P(flag), *par, objective, P(x_next), P(x0), P(al),
+           N, ps, c.st)
+    return [x_next, x0] + ([al] if alias else [])
+
+
+def q_sample_philox_case(c, shape, objective, N=3):
+    ps, off = IMAGE_SHAPES.get(shape, (shape, 0))
+    n = max(N * ps, 1)
+    x0, y = rand_off(c, 211, n, off), rand_off(c, 212, n, off)
+    m_tab, var_tab = schedule(c)
+    x_t, target = zeros_off(c, n, off), zeros_off(c, n, off)
+    seed, ordinal, t = per_image(c, [11, 12, 13], N), per_image(c, [0, 5, 2 ** 33], N), per_image(c, [7, 4, 1], N)
+    c.call("bbdm_bb_q_sample_philox_f32", P(x0), P(y), P(seed), P(ordinal), P(t), P(m_tab), P(var_tab), P(x_t), P(target), N, ps, objective, c.st)
+    return [x_t, target]
+
+
+def q_sample_cached_case(c, shape, philox, stats, objective, bad, N=3):
+    """Rows gathered from a cache of M = 4; hw = per_sample / 3 for 1032 (three channels), 7 for 7; `bad`: one index = M (NaN fill)."""
+    ps, off = IMAGE_SHAPES.get(shape, (shape, 0))
+    M, hw = 4, (344 if ps == 1032 else max(ps, 1))
+    n = max(N * ps, 1)
+    C = max(ps // hw, 1)
+    ori, cond = rand_off(c, 221, M * max(ps, 1), off), rand_off(c, 222, M * max(ps, 1), off)
+    idx_ori, idx_cond = per_image(c, [2, M if bad else 0, 3], N), per_image(c, [1, 3, 0], N)
+    st = [c.rand(223, C), c.rand(224, C).abs() + 0.5, c.rand(225, C), c.rand(226, C).abs() + 0.5] if stats else [None] * 4
+    seed, ordinal, t = per_image(c, [11, 12, 13], N), per_image(c, [0, 5, 2 ** 33], N), per_image(c, [7, 4, 1], N)
+    noise = None if philox else rand_off(c, 227, n, off)
+    m_tab, var_tab = schedule(c)
+    x_t, target, y_out = zeros_off(c, n, off), zeros_off(c, n, off), zeros_off(c, n, off)
+    head = (P(ori), P(cond), M, P(idx_ori), P(idx_cond), *map(P, st), hw)
+    tail = (P(t), P(m_tab), P(var_tab), P(x_t), P(target), P(y_out), N, ps, objective, c.st)
+    if philox:
+        c.call("bbdm_bb_q_sample_cached_philox_f32", *head, P(seed), P(ordinal), *tail)
+    else:
+        c.call("bbdm_bb_q_sample_cached_f32", *head, P(noise), *tail)
+    return [x_t, target, y_out]
+
+
+def philox_normal_case(c, shape, domain, N=3):
+    ps, off = IMAGE_SHAPES.get(shape, (shape, 0))
+    out = zeros_off(c, max(N * ps, 1), off)
+    seed, ordinal = per_image(c, [11, 12, 13], N), per_image(c, [0, 5, 2 ** 33], N)
+    c.call("bbdm_philox_normal_f32", P(out), P(seed), P(ordinal), domain, N, ps, c.st)
+    return [out]
+
+
+def p_step_scalar_case(c, is_last, clip, objective, alias):
+    N, ps = 3, 7
+    n = N * ps
+    x_t, y, pred, noise = c.rand(231, n), c.rand(232, n), c.rand(233, n), c.rand(234, n)
+    m_tab, var_tab = schedule(c)
+    x_next, x0, al = c.zeros(n), c.zeros(n), (c.zeros(n) if alias else None)
+    c.call("bbdm_bb_p_sample_step_f32", P(x_t), P(y), P(pred), P(noise), P(m_tab), P(var_tab), 7, 5, is_last, 0.75, clip, objective,
+           P(x_next), P(x0), P(al), N, ps, c.st)
+    return [x_next, x0] + ([al] if alias else [])
+
+
+def q_sample_scalar_case(c, which, objective):
+    N, ps = 3, 7
+    n = N * ps
+    a, b, e = c.rand(241, n), c.rand(242, n), c.rand(243, n)
+    m_tab, var_tab = schedule(c)
+    t = ints(c, [7, 4, 1])
+    if which == "q_sample":
+        x_t, target = c.zeros(n), c.zeros(n)
+        c.call("bbdm_bb_q_sample_f32", P(a), P(b), P(e), P(t), P(m_tab), P(var_tab), P(x_t), P(target), N, ps, objective, c.st)
+        return [x_t, target]
+    x0 = c.zeros(n)
+    c.call("bbdm_bb_predict_x0_f32", P(a), P(b), P(e), P(t), P(m_tab), P(var_tab), P(x0), N, ps, objective, c.st)
+    return [x0]
+
+
+def loss_case(c, bwd, count, loss_type):
+    a, b = c.rand(251, count), c.rand(252, count)
+    if bwd:
+        dpred = c.zeros(count)
+        gscale = c.scalar(0.5)
+        c.call("bbdm_bb_loss_bwd_f32", P(a), P(b), P(gscale), P(dpred), count, loss_type, c.st)
+        return [dpred]
+    cell, out = c.zeros(4, c.torch.int64), c.zeros(1)
+    c.call("bbdm_bb_loss_f32", P(a), P(b), P(cell), P(out), count, loss_type, c.st)
+    return [cell, out]
+
+
+def layout_case(c, to_nhwc, Cb):
+    N, H, W, Ca, Cpad, ld = 2, 3, 5, 3, 4, 4
+    if to_nhwc:
+        a, b = c.rand(261, N * Ca * H * W), (c.rand(262, N * Cb * H * W) if Cb else None)
+        out = c.zeros(N * H * W * ld)
+        c.call("bbdm_nchw_to_nhwc_f32", P(a), Ca, P(b), Cb, P(out), ld, Cpad, N, H, W, c.st)
+    else:
+        x, out = c.rand(263, N * H * W * ld), c.zeros(N * Ca * H * W)
+        c.call("bbdm_nhwc_to_nchw_f32", P(x), ld, P(out), N, H, W, Ca, c.st)
+    return [out]
+
+
+def philox_raw_case(c, n):
+    g = c.torch.Generator().manual_seed(271)
+    ck = c.torch.randint(-2 ** 31, 2 ** 31, (n, 6), generator=g, dtype=c.torch.int64).to(c.torch.int32).to(c.dev)
+    out = c.zeros(4 * n, c.torch.int32)
+    c.call("bbdm_philox_raw_u32", P(ck), P(out), n, c.st)
+    return [out]
+
+
+def latent_stats_case(c, hw, row_blocks):
+    M, C = 5, 3
+    z = c.rand(281, M * C * hw)
+    cells = c.zeros(2 * C * 4, c.torch.int64)
+    mean, var, stdev = c.zeros(C), c.zeros(C), c.zeros(C)
+    c.call("bbdm_latent_channel_stats_f32", P(z), M, C, hw, P(cells), P(mean), P(var), P(stdev), row_blocks, c.st)
+    return [cells, mean, var, stdev]
+
+
+def opt_table(c, mom, sq, nan=False):
+    """-> (device table, chunks, every buffer).  Rows as bbdm_amd.optim._ChunkTable lays them out: 16 390 elements with every pointer
+    aligned (a full chunk and a tail chunk), 16 390 one float past an alignment, 3 without a gradient, 16 384 without a shadow."""
+    ce = c.lib.bbdm_opt_chunk_elems()
+    rows, bufs = [], []
+    for i, (n, off, has_g, has_s) in enumerate(((16390, 0, 1, 1), (16390, 1, 1, 1), (3, 0, 0, 1), (16384, 0, 1, 0))):
+        p = rand_off(c, 300 + 10 * i, n, off)
+        g = rand_off(c, 301 + 10 * i, n, off, scale=0.1) if has_g else None
+        m = rand_off(c, 302 + 10 * i, n, off, scale=0.1) if mom else None
+        v = rand_off(c, 303 + 10 * i, n, off, scale=0.1).abs() if sq else None
+        s = rand_off(c, 304 + 10 * i, n, off) if has_s else None
+        if nan and i == 0:
+            g[5] = float("nan")
+        rows.append((p, g, m, v, s))
+        bufs += [x for x in (p, g, m, v, s) if x is not None]
+    ent = []
+    for p, g, m, v, s in rows:
+        for o in range(0, p.numel(), ce):
+            ent.append([0 if x is None else x.data_ptr() + 4 * o for x in (p, g, m, v, s)] + [min(ce, p.numel() - o)])
+    return c.torch.tensor(ent, dtype=c.torch.int64).to(c.dev), len(ent), bufs
+
+
+def arg(v):
+    return v.data_ptr() if hasattr(v, "data_ptr") else v
+
+
+def clip_args(c, clip):
+    """plain: the entry without a clip buffer; "coef": {norm, coef < 1, ok}; "skip": a non-finite norm under skip_nonfinite."""
+    if clip == "plain":
+        return "_f32", ()
+    buf = floats(c, [2.0, 0.5, 1.0, 0.0] if clip == "coef" else [float("nan"), float("nan"), 0.0, 0.0])
+    return "_clip_f32", (buf, 1 if clip == "skip" else 0)
+
+
+def adam_case(c, do_adam, wd, ema_mode, step, clip):
+    table, n, bufs = opt_table(c, True, True)
+    sfx, extra = clip_args(c, clip)
+    c.call("bbdm_adam_ema_step" + sfx, P(table), n, do_adam, 1e-3, 0.9, 0.999, 1e-8, wd, step, ema_mode, 0.999, *map(arg, extra), c.st)
+    return bufs
+
+
+def sgd_case(c, momentum, nesterov, first, dampening, clip):
+    table, n, bufs = opt_table(c, momentum != 0, False)
+    sfx, extra = clip_args(c, clip)
+    c.call("bbdm_sgd_ema_step" + sfx, P(table), n, 1e-2, momentum, dampening, 0.01, nesterov, first, 1, 0.999, *map(arg, extra), c.st)
+    return bufs
+
+
+def rmsprop_case(c, momentum, ema_mode, clip):
+    table, n, bufs = opt_table(c, momentum != 0, True)
+    sfx, extra = clip_args(c, clip)
+    c.call("bbdm_rmsprop_ema_step" + sfx, P(table), n, 1e-2, 0.99, 1e-8, 0.01, momentum, ema_mode, 0.999, *map(arg, extra), c.st)
+    return bufs
+
+
+def grad_norm_case(c, max_norm, nan, scale):
+    table, n, bufs = opt_table(c, False, False, nan=nan)
+    cells = c.zeros(c.lib.bbdm_grad_norm_cells_bytes() // 8, c.torch.int64)
+    out, skipped = c.zeros(4), c.zeros(1, c.torch.int64)
+    c.call("bbdm_grad_sqnorm_f32", P(table), n, P(cells), c.st)
+    c.call("bbdm_grad_norm_finalize_f32", P(cells), max_norm, P(out), P(skipped), c.st)
+    if scale:
+        c.call("bbdm_grad_scale_f32", P(table), n, P(out), c.st)
+    return [cells, out, skipped] + bufs
+
+
+def loss_meter_case(c, per_sample, off, loss_type, want_image, stage):
+    """stage "per_image"; "accumulate": + a t vector with one negative value and one >= T; "read": + the table read back."""
+    N, T, B = 3, 10, 4
+    a, b = rand_off(c, 401, N * per_sample, off), rand_off(c, 402, N * per_sample, off)
+    cells = c.zeros(N * 4, c.torch.int64)
+    per_image = c.zeros(N) if want_image else None
+    c.call("bbdm_loss_meter_per_image_f32", P(a), P(b), P(cells), P(per_image), N, per_sample, loss_type, c.st)
+    outs = [cells] + ([per_image] if want_image else [])
+    if stage == "per_image":
+        return outs
+    meter, counts = c.zeros(2 * B * 4, c.torch.int64), c.zeros(B + 1, c.torch.int64)
+    t = ints(c, [-1, 5, 12])
+    c.call("bbdm_loss_meter_accumulate", P(cells), P(t), P(meter), P(counts), N, per_sample, T, B, c.st)
+    outs += [meter, counts]
+    if stage == "read":
+        s, sq = c.zeros(B, c.torch.float64), c.zeros(B, c.torch.float64)
+        c.call("bbdm_loss_meter_read", P(meter), P(s), P(sq), B, c.st)
+        outs += [s, sq]
+    return outs
+
+
+def elementwise_grid():
+    prod = itertools.product
+    forms = ("batched", "requests", "philox", "requests_philox")
+    for form, shape, objective, clip, alias in prod(forms, IMAGE_SHAPES, (0, 1, 2), (0, 1), (0, 1)):
+        yield "p_step_image", dict(form=form, shape=shape, objective=objective, clip=clip, alias=alias), p_step_image_case
+    for shape, objective in prod(IMAGE_SHAPES, (0, 1, 2)):
+        yield "q_sample_philox", dict(shape=shape, objective=objective), q_sample_philox_case
+    for shape, philox, stats, objective, bad in prod(IMAGE_SHAPES, (0, 1), (0, 1), (0, 1, 2), (0, 1)):
+        yield "q_sample_cached", dict(shape=shape, philox=philox, stats=stats, objective=objective, bad=bad), q_sample_cached_case
+    for shape, domain in prod(IMAGE_SHAPES, (0, 1)):
+        yield "philox_normal", dict(shape=shape, domain=domain), philox_normal_case
+    for is_last, clip, objective, alias in prod((0, 1), (0, 1), (0, 1, 2), (0, 1)):
+        yield "p_step_scalar", dict(is_last=is_last, clip=clip, objective=objective, alias=alias), p_step_scalar_case
+    for which, objective in prod(("q_sample", "predict_x0"), (0, 1, 2)):
+        yield "q_sample_scalar", dict(which=which, objective=objective), q_sample_scalar_case
+    for bwd, count, loss_type in prod((0, 1), (7, 5000), (0, 1)):
+        yield "loss", dict(bwd=bwd, count=count, loss_type=loss_type), loss_case
+    for to_nhwc, Cb in ((1, 1), (1, 0), (0, 0)):
+        yield "layout", dict(to_nhwc=to_nhwc, Cb=Cb), layout_case
+    yield "philox_raw", dict(n=5), philox_raw_case
+    for hw, row_blocks in prod((8, 7), (0, 2)):
+        yield "latent_stats", dict(hw=hw, row_blocks=row_blocks), latent_stats_case
+    for do_adam, wd, ema_mode, step, clip in prod((0, 1), (0.0, 0.01), (0, 1, 2), (1, 7), ("plain", "coef", "skip")):
+        yield "adam", dict(do_adam=do_adam, wd=wd, ema_mode=ema_mode, step=step, clip=clip), adam_case
+    for momentum, nesterov, first, dampening, clip in prod((0.0, 0.9), (0, 1), (0, 1), (0.0, 0.1), ("plain", "coef")):
+        yield "sgd", dict(momentum=momentum, nesterov=nesterov, first=first, dampening=dampening, clip=clip), sgd_case
+    for momentum, ema_mode, clip in prod((0.0, 0.9), (0, 1, 2), ("plain", "coef", "skip")):
+        yield "rmsprop", dict(momentum=momentum, ema_mode=ema_mode, clip=clip), rmsprop_case
+    for max_norm, nan in prod((float("inf"), 0.5), (0, 1)):
+        yield "grad_norm", dict(max_norm=max_norm, nan=nan, scale=0), grad_norm_case
+    yield "grad_norm", dict(max_norm=0.5, nan=0, scale=1), grad_norm_case
+    for per_sample, off, loss_type, want_image in prod((7, 2052), (0, 1), (0, 1), (0, 1)):
+        yield "loss_meter", dict(per_sample=per_sample, off=off, loss_type=loss_type, want_image=want_image, stage="per_image"), loss_meter_case
+    for stage in ("accumulate", "read"):
+        yield "loss_meter", dict(per_sample=7, off=0, loss_type=1, want_image=0, stage=stage), loss_meter_case
+    # refusals: the error text must match too
+    for N, shape in ((65536, 1), (3, 0)):
+        for form in forms:
+            yield "p_step_image", dict(form=form, shape=shape, objective=0, clip=0, alias=0, N=N), p_step_image_case
+        yield "q_sample_philox", dict(shape=shape, objective=0, N=N), q_sample_philox_case
+        for philox in (0, 1):
+            yield "q_sample_cached", dict(shape=shape, philox=philox, stats=0, objective=0, bad=0, N=N), q_sample_cached_case
+        yield "philox_normal", dict(shape=shape, domain=0, N=N), philox_normal_case
+    yield "adam", dict(do_adam=1, wd=0.0, ema_mode=3, step=1, clip="plain"), adam_case
+    yield "rmsprop", dict(momentum=0.0, ema_mode=3, clip="plain"), rmsprop_case
+
+
 def grid():
     prod = itertools.product
     for m, pre, up, form, idx64 in prod((2, 4, 6, 7, 8), (0, 1), (0, 1), INPUT_FORMS, (0, 1)):
@@ -461,6 +759,7 @@ def grid():
         yield "linear", dict(N=N, In=In, Out=Out, packed=0), linear_case
     for N, In in ((8, 64), (32, 512)):
         yield "linear", dict(N=N, In=In, Out=96, packed=1), linear_case
+    yield from elementwise_grid()
 
 
 def child(path, emu, out_path):
