@@ -9,6 +9,11 @@
 // model/VQGAN/quantize.py:271-286 (VectorQuantizer2.forward): nearest codebook entry,
 //     d = sum(z^2, 1) + sum(e^2, 1) - 2 z e^T;  argmin_j d
 // e_dim is 3..8: one thread evaluates a pixel against the codebook streamed through LDS.
+//
+// Built with -ffp-contract=off (Makefile): the only fused multiply-adds are the fmaf() written out below.  Contracted, the softmax's
+// r * scale - m became fma(r, scale, -m) against a maximum m that WAS rounded -- the row maximum's exponent then is the rounding
+// residual of r * scale instead of 0 -- and zz / ee of the codebook search were no longer the sums of rounded squares that the
+// reference expression computes.
 #include "common.h"
 #include "dispatch.h"
 

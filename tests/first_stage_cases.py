@@ -24,12 +24,13 @@ def make(dev, seed=0, **over):
     return m.eval().to(dev)
 
 
-def encode_decode_parity(dev, N=2, tol=2e-4, **over):
-    m = make(dev, **over)
-    ref = make(torch.device("cpu"), **over)
+def encode_decode_parity(dev, N=2, tol=2e-4, x=None, size=None, models=None, **over):
+    """``x``: the images (default: N of clamp(randn), ``size`` pixels square); ``models``: a (HIP, PyTorch) pair whose plans are reused."""
+    m, ref = models if models is not None else (make(dev, **over), make(torch.device("cpu"), **over))
     g = torch.Generator().manual_seed(7)
-    S = DD["resolution"]
-    x = torch.randn(N, 3, S, S, generator=g).clamp(-1, 1)
+    S = size or DD["resolution"]
+    if x is None:
+        x = torch.randn(N, 3, S, S, generator=g).clamp(-1, 1)
     with torch.no_grad():
         z_ref = ref.quant_conv(ref.encoder(x))
         z_pre = ref.encoder(x)
@@ -48,6 +49,64 @@ def encode_decode_parity(dev, N=2, tol=2e-4, **over):
         img_ref2 = ref.decode(ref.quantize(ref.quant_conv(z_pre))[0])
     assert rel_err(m.decode_latent(z_pre.to(dev), quant_conv_first=True).cpu(), img_ref2) < tol
     return m
+
+
+def width1_gemm_layout_parity(dev, N):
+    """24 x 24 images, attention at 12 x 12 and (middle block) 6 x 6: 144 and 36 tokens, neither a multiple of 32 -- the batched GEMM's
+    image-of-width-1 layout, K chunks and row tiles with tails, and a 6 x 6 Winograd level."""
+    encode_decode_parity(dev, N=N, size=24, resolution=24, attn_resolutions=[12])
+
+
+def no_resample_conv_parity(dev, N):
+    """resamp_with_conv=False: the average-pool branch of ``_down`` and the bare nearest-upsample branch of ``_up``."""
+    encode_decode_parity(dev, N=N, resamp_with_conv=False)
+
+
+def structured_images():
+    """Inputs that look like image content rather than clamp(randn): constant, one hot pixel on -1, +-1 checkerboard, a vertical step
+    edge, a nearly constant image (GroupNorm of a tiny variance)."""
+    S = DD["resolution"]
+    g = torch.Generator().manual_seed(21)
+    const = torch.full((1, 3, S, S), 0.5)
+    hot = torch.full((1, 3, S, S), -1.0)
+    hot[:, :, S // 2 + 1, S // 3] = 1.0
+    yy, xx = torch.meshgrid(torch.arange(S), torch.arange(S), indexing="ij")
+    checker = (((yy + xx) % 2) * 2.0 - 1.0).expand(1, 3, S, S).contiguous()
+    step = torch.where(xx < S // 2 - 1, -0.8, 0.6).expand(1, 3, S, S).contiguous()
+    flat = 0.3 + 1e-3 * torch.randn(1, 3, S, S, generator=g)
+    return {"constant": const, "hot pixel": hot, "checkerboard": checker, "step edge": step, "nearly constant": flat}
+
+
+def structured_images_and_repeated_calls(dev, tol=2e-4):
+    """Every image of :func:`structured_images` alone (its error relative to its own magnitude) through ONE encode plan and ONE decode
+    plan: the latent against the PyTorch first stage's, then a perturbed reference latent into both decoders -- code indices bit-equal,
+    image within ``tol``.  After the five different inputs the first one runs again: both calls must return what they returned the
+    first time, bit for bit (nothing may survive in the reused scratch: the pack buffer shared by k and v, the statistics
+    accumulators, the split-K workspace)."""
+    m, ref = make(dev), make(torch.device("cpu"))
+    g = torch.Generator().manual_seed(23)
+    first = None
+    for name, x in structured_images().items():
+        with torch.no_grad():
+            z_ref = ref.quant_conv(ref.encoder(x))
+            zl = z_ref + 0.05 * torch.randn(z_ref.shape, generator=g)
+            zq_ref, _, (_, _, idx_ref) = ref.quantize(zl)
+            img_ref = ref.decode(zq_ref)
+        z = m.encode_latent(x.to(dev))
+        img, idx = m.decode_latent(zl.to(dev), return_indices=True)
+        e_z, e_img = rel_err(z.cpu(), z_ref), rel_err(img.cpu(), img_ref)
+        print(f"structured image '{name}': encode rel err {e_z:.2e}, decode rel err {e_img:.2e}")
+        assert e_z < tol and e_img < tol, name
+        assert torch.equal(idx.cpu().flatten(), idx_ref.flatten()), name
+        if first is None:
+            first = (x, zl, z.clone(), img.clone(), idx.clone())
+    assert len(m._fs_plans) == 2
+    x, zl, z1, img1, idx1 = first
+    z2 = m.encode_latent(x.to(dev))
+    img2, idx2 = m.decode_latent(zl.to(dev), return_indices=True)
+    assert len(m._fs_plans) == 2
+    assert torch.equal(z1, z2), "encode_latent: a second call on the same plan differs"
+    assert torch.equal(idx1, idx2) and torch.equal(img1, img2), "decode_latent: a second call on the same plan differs"
 
 
 def vq_indices_bit_exact(dev):

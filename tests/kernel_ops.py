@@ -197,15 +197,18 @@ def groupnorm_stats(x: torch.Tensor, groups: int = 32) -> torch.Tensor:
 
 def groupnorm_apply(x: torch.Tensor, stats: Optional[torch.Tensor], gamma: Optional[torch.Tensor],
                     beta: Optional[torch.Tensor], film: Optional[torch.Tensor] = None, eps: float = 1e-5,
-                    silu: bool = False, resample: int = 0, groups: int = 32) -> torch.Tensor:
-    """film: [N, 2C] (scale | shift).  resample: 0 none, 1 avg-pool 2x2, 2 nearest x2."""
-    _chk(x, stats, gamma, beta, film)
+                    silu: bool = False, resample: int = 0, groups: int = 32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """film: [N, 2C] (scale | shift).  resample: 0 none, 1 avg-pool 2x2, 2 nearest x2, 3 / 4 keep the even / odd positions of both
+    axes ([N, H/2, W/2, C]).  ``out``: a destination [N, Ho, Wo, ldy >= C] (its last dimension is the pitch; columns >= C stay)."""
+    _chk(x, stats, gamma, beta, film, out)
     N, H, W, C = x.shape
-    Ho, Wo = (H // 2, W // 2) if resample == 1 else ((2 * H, 2 * W) if resample == 2 else (H, W))
-    y = torch.empty(N, Ho, Wo, C, dtype=torch.float32, device=x.device)
+    Ho, Wo = (H // 2, W // 2) if resample in (1, 3, 4) else ((2 * H, 2 * W) if resample == 2 else (H, W))
+    y = torch.empty(N, Ho, Wo, C, dtype=torch.float32, device=x.device) if out is None else out
+    if tuple(y.shape[:3]) != (N, Ho, Wo):
+        raise ValueError(f"groupnorm_apply: out is {tuple(y.shape)}, expected ({N}, {Ho}, {Wo}, >= {C})")
     _lib.call("bbdm_groupnorm_apply_f32", x.data_ptr(), C, None if stats is None else stats.data_ptr(),
               None if gamma is None else gamma.data_ptr(), None if beta is None else beta.data_ptr(),
-              None if film is None else film.data_ptr(), 0 if film is None else film.shape[1], y.data_ptr(), C,
+              None if film is None else film.data_ptr(), 0 if film is None else film.shape[1], y.data_ptr(), y.shape[-1],
               N, H, W, C, groups, float(eps), 1 if silu else 0, resample, _st(x))
     return y
 
@@ -568,15 +571,60 @@ def geglu_bwd(a, dy):
     return da
 
 
-def vq_nearest(z: torch.Tensor, codebook: torch.Tensor):
-    """z: [pixels, e_dim], codebook: [n_e, e_dim] -> (int64 indices [pixels], nearest rows [pixels, e_dim])."""
+def vq_nearest(z: torch.Tensor, codebook: torch.Tensor, e_dim: Optional[int] = None, ldq: Optional[int] = None,
+               want_idx: bool = True, want_zq: bool = True, zq_fill: Optional[float] = None):
+    """z: [pixels, ldz >= e_dim], codebook: [n_e, e_dim] -> (int64 indices [pixels], nearest rows [pixels, ldq]); an output that is not
+    wanted is passed as NULL and returned as None.  ``e_dim`` defaults to z's width, ``ldq`` to e_dim; ``zq_fill`` prefills the rows
+    (columns >= e_dim are never written)."""
     _chk(z, codebook)
-    P, D = z.shape
-    idx = torch.empty(P, dtype=torch.int64, device=z.device)
-    zq = torch.empty(P, D, dtype=torch.float32, device=z.device)
-    _lib.call("bbdm_vq_nearest_f32", z.data_ptr(), D, codebook.data_ptr(), idx.data_ptr(), zq.data_ptr(), D, P,
-              codebook.shape[0], D, _st(z))
+    P, ldz = z.shape
+    D = ldz if e_dim is None else e_dim
+    ldq = D if ldq is None else ldq
+    idx = torch.empty(P, dtype=torch.int64, device=z.device) if want_idx else None
+    zq = None
+    if want_zq:
+        zq = torch.empty(P, max(ldq, 1), dtype=torch.float32, device=z.device)
+        if zq_fill is not None:
+            zq.fill_(zq_fill)
+    _lib.call("bbdm_vq_nearest_f32", z.data_ptr(), ldz, codebook.data_ptr(), None if idx is None else idx.data_ptr(),
+              None if zq is None else zq.data_ptr(), ldq, P, codebook.shape[0], D, _st(z))
     return idx, zq
+
+
+def gemm_packed_b_floats(R: int, K: int) -> int:
+    return int(_lib.load().bbdm_gemm_packed_b_floats(R, K))
+
+
+def gemm_pack_b(b: torch.Tensor, R: int, K: int, transposed: bool, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """b: [batch, rows, ldb] -- per batch element a row-major [R x K] matrix (out = A B^T) or, ``transposed``, [K x R] (out = A B) in the
+    leading columns; pitch and batch stride are the tensor's.  -> the packed operand of :func:`gemm_batched`
+    (batch * bbdm_gemm_packed_b_floats(R, K) floats; ``packed``: a caller's buffer of at least that size)."""
+    _chk(b, packed)
+    batch, brows, ldb = b.shape
+    if packed is None:
+        packed = torch.empty(batch * gemm_packed_b_floats(R, K), dtype=torch.float32, device=b.device)
+    _lib.call("bbdm_gemm_pack_b_f32", b.data_ptr(), ldb, brows * ldb, packed.data_ptr(), batch, R, K, 1 if transposed else 0, _st(b))
+    return packed
+
+
+def gemm_batched(a: torch.Tensor, packed: torch.Tensor, rows: int, K: int, R: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a: [batch, >= rows, lda >= K] (pitch and batch stride are the tensor's) -> out [batch, >= rows, ldo >= R] with
+    out_b[:rows, :R] = a_b[:rows, :K] . B_b."""
+    _chk(a, packed, out)
+    batch, arows, lda = a.shape
+    if out is None:
+        out = torch.empty(batch, rows, R, dtype=torch.float32, device=a.device)
+    _lib.call("bbdm_gemm_batched_f32", a.data_ptr(), lda, arows * lda, packed.data_ptr(), out.data_ptr(), out.shape[2],
+              out.shape[1] * out.shape[2], batch, rows, K, R, _st(a))
+    return out
+
+
+def softmax_rows(s: torch.Tensor, T: int, scale: float) -> torch.Tensor:
+    """In place: softmax(scale * s[..., :T]) over the leading T columns of every row (pitch = s.shape[-1])."""
+    _chk(s)
+    ld = s.shape[-1]
+    _lib.call("bbdm_softmax_rows_f32", s.data_ptr(), ld, s.numel() // ld, T, float(scale), _st(s))
+    return s
 
 
 def conv1x1_bf3q(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], residual: Optional[torch.Tensor] = None,

@@ -30,6 +30,18 @@ def test_encode_decode_match_the_pytorch_first_stage(dev):
     C.encode_decode_parity(dev, N=3)
 
 
+def test_token_counts_on_the_width1_gemm_layout(dev):
+    C.width1_gemm_layout_parity(dev, N=3)
+
+
+def test_resample_without_conv(dev):
+    C.no_resample_conv_parity(dev, N=3)
+
+
+def test_structured_images_and_repeated_calls(dev):
+    C.structured_images_and_repeated_calls(dev)
+
+
 def test_vq_f4_geometry_and_rate(dev):
     over = dict(z_channels=3, resolution=256, ch=128, ch_mult=(1, 2, 4), num_res_blocks=2, attn_resolutions=[])
     old = dict(C.DD)

@@ -1,5 +1,8 @@
 """Kernel-level parity (GPU): every C-ABI entry point against the same op in plain PyTorch fp32 on the CPU
-(F.conv2d, F.group_norm, softmax attention, F.linear, the scheduler formulas of the oracle).
+(F.conv2d, F.group_norm, softmax attention, F.linear, the scheduler formulas of the oracle).  The entry points only the VQGAN
+first stage calls -- bbdm_gemm_pack_b_f32 / bbdm_gemm_batched_f32 / bbdm_gemm_packed_b_floats, bbdm_softmax_rows_f32,
+bbdm_groupnorm_apply_f32 with resample 3 and 4, bbdm_vq_nearest_f32 beyond e_dim == pitch -- are in
+tests/test_first_stage_kernels_gpu.py (bodies: tests/first_stage_kernel_cases.py), against fp64.
 
 Tolerances: fp32 arithmetic with a different summation order -> 2e-5 relative to the output's max magnitude
 (the north-star bar is 1e-3 per sampling step for the whole UNet)."""
